@@ -9,7 +9,14 @@ Finished games restart immediately.  Data: synthetic — empty boards, random-in
 half-size engines on two HIP streams (15x15 MuZero default; engine.SplitSelfPlayEngine: the same games
 as one engine, bit for bit; one half's tree/head kernels overlap the other half's tower).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up moves, the K timed moves
+(with the HIP events of ``roofline`` / ``roofline_tree`` around the two dominant kernels, as ever), the
+outputs of the last timed move to DIR when ``--dump-outputs`` is given (<name>.npy, float64: policy,
+root_value, action, status), and the line.  ``--full`` adds every other leg listed below (each with its own
+switch: --sublines, --worker-moves, --trainer-steps, --loop-iters, --single-stream-moves,
+--no-cpu-baseline); without ``--full`` those switches are not consulted.
 
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) the ranks are the
 launcher's; with WORLD_SIZE unset, ``--gpus N`` starts the N rank processes itself (before anything
@@ -23,10 +30,12 @@ Prints ONE JSON line on rank 0 (schema: the driver contract) including
                   launch stream(s) inside the timed region; achieved = algorithmic FLOP of the rows the
                   searches actually requested / the kernel's busy time (union of its launch intervals
                   over both streams; = launches x mean duration with one stream) vs the 2.5 PFLOP/s
-                  dense f16/bf16 MFMA peak; per-launch figures beside it;
+                  dense f16/bf16 MFMA peak; per-launch figures beside it (``achievable``, the live GEMM / copy
+                  peaks measured after the timed region, and ``single_stream_kernels``: --full only);
   roofline_tree : the fused expand/backup + select kernel (k_expand_select), same timing; achieved =
                   algorithmic bytes counted from the per-game work counters (gmz_engine_tree_counters,
                   byte model in DESIGN.md §5) / its busy time vs 8 TB/s HBM;
+and, with --full,
   trainer       : config C4's trainer (B = 360 per GPU, 5 unroll steps, PER, fp16 autocast, HIP convs),
                   steps/s after the self-play region, on every rank (DDP: one RCCL gradient all-reduce +
                   the sharded-PER syncs per step), plus the MFMA fraction of its dominant HIP conv;
@@ -153,6 +162,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the live achievable peaks, the single-stream kernel times, the "
+                         "sub-lines, the drop-in worker leg, the trainer, the C4 loop and the CPU baseline (each "
+                         "with its own switch below); off: the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed moves, write what the last of them returned (search: policy, root_value, "
+                         "action; play: status; every game of this rank) as DIR/<name>.npy in float64")
     ap.add_argument("--games", type=int, default=1024, help="concurrent games per GPU (config 2: 1024)")
     ap.add_argument("--size", type=int, default=15)
     ap.add_argument("--sims", type=int, default=400)
@@ -241,6 +257,14 @@ def parse(argv=None):
     ap.add_argument("--pmc-file", default=os.path.join(REPO, "profiles", "pmc_tower_latest.json"))
     ap.add_argument("--pmc-tree-file", default=os.path.join(REPO, "profiles", "pmc_tree_latest.json"))
     return ap.parse_args(argv)
+
+
+def headline_only(args):
+    """A plain run (no --full): every leg besides the headline is switched off, whatever its own switch says
+    (the live achievable peaks go with ``args.full`` itself, run_phase)."""
+    args.sublines, args.worker_moves, args.trainer_steps, args.loop_iters = "", 0, 0, 0
+    args.single_stream_moves, args.no_cpu_baseline = 0, True
+    return args
 
 
 def _free_port():
@@ -601,14 +625,27 @@ def trainer_trace_summary(args):
     return out
 
 
+def dump_outputs(dump_dir, arrays, rank=0):
+    """--dump-outputs: each array as <dump_dir>/<name>.npy (rank 0; rank r > 0, whose games are others:
+    <name>.rank<r>.npy), float64.  The inputs (weights, start positions, the device noise's seed) depend on
+    the arguments alone, so two builds run with the same arguments can be compared file by file.  Returns
+    the names written."""
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + (".rank%d" % rank if rank else "") + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def selfplay_leg(args, rank, world, dist, backend, size, sims, mode, blocks, G, steps, warmup, streams=None,
-                 single_stream_moves=0, log_prefix="", openings=None):
+                 single_stream_moves=0, log_prefix="", openings=None, dump_dir=None):
     """G games of (size, sims, mode, blocks) self-play on this rank's GPU: ``warmup`` untimed moves, then
     ``steps`` timed moves (barrier + synchronize on both sides, max over ranks).  ``openings``: the games'
     start positions (engine.seeded_openings; None = empty boards).  Returns a dict with dt (s, max over
     ranks), rank_dt (every rank's own time), finished_games (games that ended in the timed moves, all
     ranks), waves, streams, roofline (dominant tower), roofline_tree and, with single_stream_moves > 0
-    and two streams, single_stream_kernels."""
+    and two streams, single_stream_kernels.  ``dump_dir``: the last timed move's outputs go there
+    (dump_outputs)."""
     import datou_gomoku_muzero_amd.engine as E
     from datou_gomoku_muzero_amd import network as N, weights as W
     from datou_gomoku_muzero_amd.config import GmzConfig
@@ -686,6 +723,10 @@ def selfplay_leg(args, rank, world, dist, backend, size, sims, mode, blocks, G, 
         dist.barrier()
     own = time.perf_counter() - t0
     dt = collective_max(own, dist, backend)
+    last = None
+    if dump_dir:  # what the last timed move returned, copied before anything else runs on the engine
+        last = {k: getattr(eng, k).to(torch.float64).cpu().numpy()
+                for k in ("policy", "root_value", "action", "status")}
     res = {"dt": dt, "waves": waves, "streams": streams, "rank_dt": collective_gather(own, dist, backend),
            "finished_games": int(collective_sum(float(finished.item()), dist, backend)),
            "step_ms": [round((b - a) * 1e3, 2) for a, b in zip(marks, marks[1:])]}
@@ -787,6 +828,8 @@ def selfplay_leg(args, rank, world, dist, backend, size, sims, mode, blocks, G, 
     eng.close()
     del eng, net
     torch.cuda.empty_cache()
+    if last is not None:
+        res["dumped"] = dump_outputs(dump_dir, last, rank)
     return res
 
 
@@ -991,7 +1034,8 @@ def run_phase(phase, args, rank, world, dist, backend, consumer=None, out=None):
         G = args.games
         r = selfplay_leg(args, rank, world, dist, backend, args.size, args.sims, args.mode, args.blocks, G,
                          args.steps, args.warmup, streams=args.streams, single_stream_moves=args.single_stream_moves,
-                         openings=headline_openings(args, rank, G, args.size))
+                         openings=headline_openings(args, rank, G, args.size),
+                         dump_dir=getattr(args, "dump_outputs", None))
         args.streams = r["streams"]
         frag = result_line(args, world, r["dt"], r["waves"], G, backend)
         frag["finished_games"] = r["finished_games"]
@@ -1000,7 +1044,10 @@ def run_phase(phase, args, rank, world, dist, backend, consumer=None, out=None):
         for k in ("roofline", "roofline_tree", "single_stream_kernels"):
             if k in r:
                 frag[k] = r[k]
-        if rank == 0 and args.net == "hip" and "roofline" in frag:  # after every timed region of this phase
+        if "dumped" in r:
+            frag["dumped_outputs"] = r["dumped"]
+        # --full: the live GEMM / copy peaks, after every timed region of this phase
+        if getattr(args, "full", False) and rank == 0 and args.net == "hip" and "roofline" in frag:
             with_achievable(frag["roofline"], "gemm_f16_tflops")
             if "roofline_tree" in frag:
                 with_achievable(frag["roofline_tree"], "copy_gbs")
@@ -1245,6 +1292,8 @@ def orchestrate(args, argv, rank, world, script=None):
 
 def main():
     args = parse()
+    if not args.full:
+        headline_only(args)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # no external launcher: one process per GPU, started here before any GPU call

@@ -367,3 +367,36 @@ def test_deadline_shrinks_a_later_phase_and_skips_the_rest(tmp_path):
     assert det["trainer"]["cap_s"] < 32 and det["trainer"]["ranks"][1]["status"].startswith("timeout")
     assert det["loop"]["ranks"][0]["status"].startswith("skipped") and "skipped" in d["loop_c4"]["error"]
     assert d["phases"]["seconds"] <= 32 + 5 and took < 60
+
+
+def test_a_plain_run_plans_the_headline_only():
+    """Without --full every leg besides the headline is off, whatever its own switch says (bench.main applies
+    bench.headline_only); with --full the switches decide, as before."""
+    import bench
+    argv = ["--sublines", "c1", "--worker-moves", "3", "--trainer-steps", "2", "--loop-iters", "2",
+            "--single-stream-moves", "2"]
+    plain = bench.parse(argv)
+    assert not plain.full and plain.dump_outputs is None
+    bench.headline_only(plain)
+    assert [n for n, _ in bench.phase_plan(plain)] == ["selfplay"]
+    assert plain.single_stream_moves == 0 and plain.no_cpu_baseline
+    full = bench.parse(["--full"] + argv)
+    assert full.full and [n for n, _ in bench.phase_plan(full)] == ["selfplay", "extras", "trainer", "loop"]
+    assert full.single_stream_moves == 2 and not full.no_cpu_baseline
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    """--dump-outputs: one <name>.npy per array, float64 whatever the device type was; ranks > 0 (other
+    games) under their own names."""
+    import numpy as np
+    import bench
+    arrays = {"action": np.arange(6, dtype=np.int32), "policy": np.linspace(0, 1, 12).reshape(3, 4),
+              "status": np.array([2, -1, 0], np.int8)}
+    assert bench.dump_outputs(str(tmp_path / "out"), arrays) == ["action", "policy", "status"]
+    bench.dump_outputs(str(tmp_path / "out"), {"action": arrays["action"] + 1}, rank=1)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a)
+    assert np.array_equal(np.load(tmp_path / "out" / "action.rank1.npy"), arrays["action"] + 1)
+    assert sorted(os.listdir(tmp_path / "out")) == ["action.npy", "action.rank1.npy", "policy.npy", "status.npy"]

@@ -78,7 +78,7 @@ def test_selfplay_records_train_and_hot_swap(tmp_path):
 
 
 def test_bench_spawns_its_own_ranks_gloo_rehearsal():
-    """`python bench.py --gpus 2` with no external launcher starts 2 rank processes (here sharing the
+    """`python bench.py --full --gpus 2` with no external launcher starts 2 rank processes (here sharing the
     one GPU over gloo); each phase (headline, extras, trainer, loop) runs as fresh rank processes under a
     wall-time cap, and rank 0 prints ONE line with n_gpus 2 and the global game count.  The trainer phase
     of rank 1 is made to fail (GMZ_BENCH_INJECT_FAIL) while rank 0 waits in its collectives: the line
@@ -90,7 +90,7 @@ def test_bench_spawns_its_own_ranks_gloo_rehearsal():
     from conftest import REPO
     env = dict(os.environ, GMZ_DIST_BACKEND="gloo", GMZ_BENCH_INJECT_FAIL="trainer:1")
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--games", "64",
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--games", "64",
                         "--size", "9", "--sims", "50", "--blocks", "1", "--steps", "2", "--warmup", "1",
                         "--trainer-steps", "2", "--trainer-warmup", "4", "--trainer-batch", "16", "--trainer-buffer", "64",
                         "--loop-iters", "4", "--loop-warmup", "4", "--loop-games", "64", "--loop-update-interval", "2",

@@ -4,7 +4,7 @@
 # -> gpurun_out/TAG/{old,new}_<i>.json and a one-line summary per build (moves/s, tower ms per launch, C1 / C5 lines)
 set -o pipefail
 TAG=$1; OLD=$2; ROUNDS=${3:-2}; shift 3
-ARGS=${@:---no-cpu-baseline --trainer-steps 0 --loop-iters 0 --worker-moves 0 --sublines c1}
+ARGS=${@:---full --no-cpu-baseline --trainer-steps 0 --loop-iters 0 --worker-moves 0 --sublines c1}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for i in $(seq 1 $ROUNDS); do

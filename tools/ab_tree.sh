@@ -7,7 +7,7 @@ shift; shift
 ARGS=${@:---steps 4 --warmup 1}
 OUT=$PWD/gpurun_out/abt_$TAG
 mkdir -p $OUT
-SP="--no-cpu-baseline --trainer-steps 0 --loop-iters 0"
+SP="--full --no-cpu-baseline --trainer-steps 0 --loop-iters 0"
 for i in 1 2 3; do
   GMZ_LIB=$OLD timeout -k 10 300 python3 bench.py $ARGS $SP > $OUT/old_$i.json 2> $OUT/old_$i.err || { echo "old failed"; tail -3 $OUT/old_$i.err; exit 1; }
   timeout -k 10 300 python3 bench.py $ARGS $SP > $OUT/new_$i.json 2> $OUT/new_$i.err || { echo "new failed"; tail -3 $OUT/new_$i.err; exit 1; }

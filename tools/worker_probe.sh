@@ -1,6 +1,6 @@
 #!/bin/bash
 # Worker leg vs the engine: staggered openings on/off, one stream vs two (bench.py's worker leg only)
-SP="--no-cpu-baseline --trainer-steps 0 --loop-iters 0 --sublines= --steps 4 --warmup 1 --single-stream-moves 0 --worker-moves 20"
+SP="--full --no-cpu-baseline --trainer-steps 0 --loop-iters 0 --sublines= --steps 4 --warmup 1 --single-stream-moves 0 --worker-moves 20"
 OUT=gpurun_out/wprobe
 mkdir -p $OUT
 for OP in 0 80; do
