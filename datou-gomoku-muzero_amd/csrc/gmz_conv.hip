@@ -17,6 +17,8 @@
 // 4 tiles per wave ran into the vector-L1 bandwidth, 256 B of weights per MFMA).  A fragments (weights) stream global -> VGPR
 // through a 3-deep register ring, shared by the waves of a channel group in L1.  Epilogue: f32 ->
 // activation dtype, 8-byte stores of 4 consecutive channels.
+// Board sizes: 6, 9, 15 and 19 (ConvSizes below; per-size position groups and residency in ConvCfg<H>).  At 19x19 the
+// image is 117 KB, so one workgroup per CU; the weight gradient there stages each board in two row bands (WgLds).
 #include <type_traits>
 
 #include "gmz_common.h"
@@ -161,6 +163,21 @@ struct BnApply {
   int relu;
 };
 
+// Board sizes the 3x3 family is built for (forward family and weight gradient): the ONE list the dispatches and their
+// error text come from.
+template <int... Hs> struct SizeList {};
+using ConvSizes = SizeList<6, 9, 15, 19>;
+
+// Per-size configuration of k_conv3 (as TowerCfg<H> in gmz_net.hip).  PG = position groups per workgroup (2 PG waves);
+// WG_PER_CU = workgroups of one CU's LDS (the padded image: 17 KB at 6x6, 33 KB at 9x9, 78 KB at 15x15, 117 KB at
+// 19x19, where only one fits) = the kernel's minimum-residency launch bound; AB = the off-by-default A/B variants
+// (BWD statistics, gmz_conv3x3_forward_bwdstats; the action stamp, gmz_conv3x3_forward_stamp) are built and accepted.
+#ifndef GMZ_CONV_PG19
+#define GMZ_CONV_PG19 2
+#endif
+template <int H> struct ConvCfg { static constexpr int PG = 2, WG_PER_CU = 2; static constexpr bool AB = H == 9 || H == 15; };
+template <> struct ConvCfg<19> { static constexpr int PG = GMZ_CONV_PG19, WG_PER_CU = 1; static constexpr bool AB = false; };
+
 // (Measured and removed: one workgroup per board computing both channel halves from one DMA — forward 33.9 vs 28.7 us,
 // profiles/r04_trainer_ab_defer_target.txt; the next board's DMA issued before the epilogue; the timing ablations of
 // profiles/r05_conv_ablations.txt and r06_conv_lds_ab.txt, built from commit 3a54982's gmz_conv.hip with GMZ_CONV_ABL.)
@@ -172,7 +189,7 @@ struct BnApply {
 // observations as one launch, each step's BatchNorm statistics over its own boards; gmz_bn_forward_seg).
 // BNA: the input is staged by the BatchNorm-apply prologue (BnApply ba) instead of the DMA of x.
 template <int H, typename T, int PG, bool BWD = false, bool PB = false, bool BNA = false>
-__global__ void __launch_bounds__(128 * PG, 2) k_conv3(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wpk,
+__global__ void __launch_bounds__(128 * PG, ConvCfg<H>::WG_PER_CU) k_conv3(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wpk,
                                                   uint16_t *__restrict__ y, int N, const uint8_t *__restrict__ mask,
                                                   double *__restrict__ stats, const uint16_t *__restrict__ addend,
                                                   BnBwd bn, ActStamp as, BnApply ba) {
@@ -570,12 +587,25 @@ __global__ void __launch_bounds__(128 * PG, 2) k_conv3(const uint16_t *__restric
 // weight gradient.
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
+//
+// Row bands (19x19): a whole board's tiles (384 dy rows + 21 x 21 x cells = 237,600 B) do not fit the 160 KB of LDS,
+// so the board is processed as NB = 2 bands of BR = 10 | 9 board rows inside the per-board loop, the accumulators
+// running on across bands.  A band holds its BR * H dy rows and — the workgroup's tap row ty being fixed — exactly the
+// x rows those need: band-local row yy is board row r0 + yy + ty - 1 (r0 = the band's first row), HP cells wide with
+// the zero border columns, so no border ROWS are stored: 192 x 288 + 10 x 21 x 288 = 115,776 B.  Same 288-B rows, same
+// transposing reads, tap columns still +RB apart.  What no DMA writes changes per band and is zeroed before the band's
+// DMA: the x row above the board (ty = 0, band 0, local row 0), the one below it (ty = 2, last band, its last local
+// row), and the dy rows between the last band's positions and a full band's; the border columns and the dy rows past
+// a full band are zeroed once.
 template <int H>
 struct WgLds {
-  static constexpr int A = H * H, KS = (A + 31) / 32, NPOS = KS * 32, RB = 288, HP = H + 2;
-  static constexpr int DY_BYTES = NPOS * RB, X_OFF = DY_BYTES, X_BYTES = HP * HP * RB;
+  static constexpr int A = H * H, RB = 288, HP = H + 2;
+  static constexpr int NB = H > 15 ? 2 : 1, BR = (H + NB - 1) / NB;  // row bands per board, board rows per band
+  static constexpr int BA = BR * H;                                  // positions of a full band (NB = 1: the board)
+  static constexpr int KS = (BA + 31) / 32, NPOS = KS * 32;
+  static constexpr int DY_BYTES = NPOS * RB, X_OFF = DY_BYTES, X_BYTES = (NB == 1 ? HP : BR) * HP * RB;
   static constexpr int BYTES = DY_BYTES + X_BYTES;
-  static constexpr int NPD = (A * RB + 1023) / 1024;        // dy DMA pieces
+  static constexpr int NPD = (BA * RB + 1023) / 1024;       // dy DMA pieces
   static constexpr int RUN = (H - 1) * RB + 256, RUN_DMA = (RUN + 1023) / 1024;  // one board row of x
 };
 
@@ -613,9 +643,11 @@ __global__ void __launch_bounds__(512, 1) k_conv3_wgrad(WgSrc src, int N, int nc
   const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
   const int ocol = (wo * 32 + 4 * pp) * 2, ccol = (wc * 64 + 4 * pp) * 2;  // this lane's column bytes
 
+  auto zero_cell = [&](uint8_t *cellp, int i) { ((uint4 *)cellp)[i & 15] = make_uint4(0, 0, 0, 0); };
   // zero what no board's DMA writes: the dy rows past the board (positions A..NPOS-1 of the last k-step) and the x
-  // image's border cells (ds_write_b128 stores, as in k_conv3)
-  {
+  // image's border cells (ds_write_b128 stores, as in k_conv3); banded: the dy rows past a full band and the x
+  // image's border columns
+  if constexpr (L::NB == 1) {
     constexpr int NTAIL = L::NPOS - A, NBORDER = 2 * HP + 2 * H;
     for (int i = tid; i < (NTAIL + NBORDER) * 16; i += 512) {
       const int k = i >> 4;
@@ -630,6 +662,12 @@ __global__ void __launch_bounds__(512, 1) k_conv3_wgrad(WgSrc src, int N, int nc
       }
       ((uint4 *)cellp)[i & 15] = make_uint4(0, 0, 0, 0);
     }
+  } else {
+    constexpr int NTAIL = L::NPOS - L::BA, NBORDER = 2 * L::BR;
+    for (int i = tid; i < (NTAIL + NBORDER) * 16; i += 512) {
+      const int k = i >> 4, kb = k - NTAIL;
+      zero_cell(k < NTAIL ? smem + (L::BA + k) * RB : xt + ((kb >> 1) * HP + (kb & 1) * (HP - 1)) * RB, i);
+    }
   }
   __syncthreads();
 
@@ -642,56 +680,117 @@ __global__ void __launch_bounds__(512, 1) k_conv3_wgrad(WgSrc src, int N, int nc
       for (int nt = 0; nt < 4; ++nt) acc[tx][mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   for (int b = chunk; b < N; b += nch) {
-    // ---- dy rows 0..A-1 and the x image interior: LDS-linear 1 KB pieces, row pads skipped
     const int sg = b / src.nps, lb = b - sg * src.nps;
     const uint8_t *sd = (const uint8_t *)(src.dy[sg] + (size_t)lb * A * CC);
     const uint8_t *sx = (const uint8_t *)(src.x[sg] + (size_t)lb * A * CC);
-    for (int j = w; j < L::NPD + H * L::RUN_DMA; j += 8) {
-      if (j < L::NPD) {
-        const int o = j * 1024 + lane * 16;
-        const int row = o / RB, ch = (o % RB) >> 4;
-        if (row < A && ch < 16)
-          __builtin_amdgcn_global_load_lds((const void *)(sd + row * 256 + ch * 16),
-                                           (__attribute__((address_space(3))) void *)(smem + j * 1024), 16, 0, 0);
-      } else {
-        const int jj = j - L::NPD, yy = jj / L::RUN_DMA, piece = jj % L::RUN_DMA;
-        const int o = piece * 1024 + lane * 16;
-        const int xx = o / RB, ch = (o % RB) >> 4;
-        if (o < L::RUN && ch < 16)
-          __builtin_amdgcn_global_load_lds((const void *)(sx + (yy * H + xx) * 256 + ch * 16),
-                                           (__attribute__((address_space(3))) void *)(xt + ((yy + 1) * HP + 1) * RB + piece * 1024),
-                                           16, 0, 0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-#pragma unroll 2
-    for (int ks = 0; ks < KS; ++ks) {
-      const int p0 = ks * 32 + 4 * g + q, p1 = p0 + 16;
-      // x rows: cell (y + ty, x) of the padded image for tap column 0; columns 1, 2 are +RB, +2 RB.
-      // Positions past the board (zero dy rows) read the last position's cells
-      const int c0 = p0 < A ? p0 : A - 1, c1 = p1 < A ? p1 : A - 1;
-      const int xb0 = ((c0 / H + ty) * HP + c0 % H) * RB + ccol, xb1 = ((c1 / H + ty) * HP + c1 % H) * RB + ccol;
-      const int ab0 = p0 * RB + ocol, ab1 = p1 * RB + ocol;
-      V af[2];
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const s16x4_t lo = tr_read(smem, ab0 + mt * 32), hi = tr_read(smem, ab1 + mt * 32);
-        af[mt] = __builtin_bit_cast(V, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
-#pragma unroll
-      for (int tx = 0; tx < 3; ++tx) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const s16x4_t lo = tr_read(xt, xb0 + tx * RB + nt * 32), hi = tr_read(xt, xb1 + tx * RB + nt * 32);
-          const V bf = __builtin_bit_cast(V, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) acc[tx][mt][nt] = M::run(af[mt], bf, acc[tx][mt][nt]);
+    if constexpr (L::NB == 1) {
+      // ---- dy rows 0..A-1 and the x image interior: LDS-linear 1 KB pieces, row pads skipped
+      for (int j = w; j < L::NPD + H * L::RUN_DMA; j += 8) {
+        if (j < L::NPD) {
+          const int o = j * 1024 + lane * 16;
+          const int row = o / RB, ch = (o % RB) >> 4;
+          if (row < A && ch < 16)
+            __builtin_amdgcn_global_load_lds((const void *)(sd + row * 256 + ch * 16),
+                                             (__attribute__((address_space(3))) void *)(smem + j * 1024), 16, 0, 0);
+        } else {
+          const int jj = j - L::NPD, yy = jj / L::RUN_DMA, piece = jj % L::RUN_DMA;
+          const int o = piece * 1024 + lane * 16;
+          const int xx = o / RB, ch = (o % RB) >> 4;
+          if (o < L::RUN && ch < 16)
+            __builtin_amdgcn_global_load_lds((const void *)(sx + (yy * H + xx) * 256 + ch * 16),
+                                             (__attribute__((address_space(3))) void *)(xt + ((yy + 1) * HP + 1) * RB + piece * 1024),
+                                             16, 0, 0);
         }
       }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+#pragma unroll 2
+      for (int ks = 0; ks < KS; ++ks) {
+        const int p0 = ks * 32 + 4 * g + q, p1 = p0 + 16;
+        // x rows: cell (y + ty, x) of the padded image for tap column 0; columns 1, 2 are +RB, +2 RB.
+        // Positions past the board (zero dy rows) read the last position's cells
+        const int c0 = p0 < A ? p0 : A - 1, c1 = p1 < A ? p1 : A - 1;
+        const int xb0 = ((c0 / H + ty) * HP + c0 % H) * RB + ccol, xb1 = ((c1 / H + ty) * HP + c1 % H) * RB + ccol;
+        const int ab0 = p0 * RB + ocol, ab1 = p1 * RB + ocol;
+        V af[2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          const s16x4_t lo = tr_read(smem, ab0 + mt * 32), hi = tr_read(smem, ab1 + mt * 32);
+          af[mt] = __builtin_bit_cast(V, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        }
+#pragma unroll
+        for (int tx = 0; tx < 3; ++tx) {
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) {
+            const s16x4_t lo = tr_read(xt, xb0 + tx * RB + nt * 32), hi = tr_read(xt, xb1 + tx * RB + nt * 32);
+            const V bf = __builtin_bit_cast(V, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) acc[tx][mt][nt] = M::run(af[mt], bf, acc[tx][mt][nt]);
+          }
+        }
+      }
+      __syncthreads();  // every wave is done with this board's tiles before the next DMA
+    } else {
+      for (int bd = 0; bd < L::NB; ++bd) {
+        const int r0 = bd * L::BR, nrows = H - r0 < L::BR ? H - r0 : L::BR, npos = nrows * H;
+        // ---- what this band's DMA leaves unwritten but the previous band's wrote: the dy rows npos..BA-1 (the last,
+        // shorter band) and the x row outside the board (local row 0 above it, local row nrows - 1 below it)
+        const int xr0 = r0 + ty - 1;  // board row of local x row 0
+        const int zrow = xr0 < 0 ? 0 : xr0 + nrows > H ? nrows - 1 : -1;
+        const int ntail = L::BA - npos, nz = ntail + (zrow >= 0 ? H : 0);
+        for (int i = tid; i < nz * 16; i += 512) {
+          const int k = i >> 4;
+          zero_cell(k < ntail ? smem + (npos + k) * RB : xt + (zrow * HP + 1 + (k - ntail)) * RB, i);
+        }
+        // ---- dy rows 0..npos-1 (board positions r0 * H + row) and the x rows inside the board
+        for (int j = w; j < L::NPD + nrows * L::RUN_DMA; j += 8) {
+          if (j < L::NPD) {
+            const int o = j * 1024 + lane * 16;
+            const int row = o / RB, ch = (o % RB) >> 4;
+            if (row < npos && ch < 16)
+              __builtin_amdgcn_global_load_lds((const void *)(sd + (r0 * H + row) * 256 + ch * 16),
+                                               (__attribute__((address_space(3))) void *)(smem + j * 1024), 16, 0, 0);
+          } else {
+            const int jj = j - L::NPD, yy = jj / L::RUN_DMA, piece = jj % L::RUN_DMA;
+            const int o = piece * 1024 + lane * 16;
+            const int xx = o / RB, ch = (o % RB) >> 4;
+            if (yy != zrow && o < L::RUN && ch < 16)
+              __builtin_amdgcn_global_load_lds((const void *)(sx + ((xr0 + yy) * H + xx) * 256 + ch * 16),
+                                               (__attribute__((address_space(3))) void *)(xt + (yy * HP + 1) * RB + piece * 1024),
+                                               16, 0, 0);
+          }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll 2
+        for (int ks = 0; ks < KS; ++ks) {
+          // the band's rows are already shifted by ty; positions past the band read its last position's cells
+          const int p0 = ks * 32 + 4 * g + q, p1 = p0 + 16;
+          const int c0 = p0 < npos ? p0 : npos - 1, c1 = p1 < npos ? p1 : npos - 1;
+          const int xb0 = (c0 / H * HP + c0 % H) * RB + ccol, xb1 = (c1 / H * HP + c1 % H) * RB + ccol;
+          const int ab0 = p0 * RB + ocol, ab1 = p1 * RB + ocol;
+          // (the whole-board k-step above, restated: sharing it through a lambda changed the 9x9 / 15x15 kernels'
+          // register allocation and schedule)
+          V af[2];
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt) {
+            const s16x4_t lo = tr_read(smem, ab0 + mt * 32), hi = tr_read(smem, ab1 + mt * 32);
+            af[mt] = __builtin_bit_cast(V, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+          }
+#pragma unroll
+          for (int tx = 0; tx < 3; ++tx) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+              const s16x4_t lo = tr_read(xt, xb0 + tx * RB + nt * 32), hi = tr_read(xt, xb1 + tx * RB + nt * 32);
+              const V bf = __builtin_bit_cast(V, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+#pragma unroll
+              for (int mt = 0; mt < 2; ++mt) acc[tx][mt][nt] = M::run(af[mt], bf, acc[tx][mt][nt]);
+            }
+          }
+        }
+        __syncthreads();  // every wave is done with this band's tiles before the next DMA
+      }
     }
-    __syncthreads();  // every wave is done with this board's tiles before the next DMA
   }
   // ---- acc[tx][mt][nt][e] = dW[o = 32 wo + 16 mt + 4 g + e][c = 64 wc + 16 nt + (lane & 15)][3 ty + tx]
   float *pc = part + (size_t)chunk * 9 * CC * CC;
@@ -739,10 +838,10 @@ static int cu_count_conv() {
   return n;
 }
 
-constexpr int CONV_PG = 2;  // position groups per workgroup: 2 -> 4 waves, 8|7 tiles per wave
-
 // two workgroups per board (one per half of the output channels), at most two per CU: a multiple of 16 (whole XCD
-// pairs; workgroups past the boards do nothing)
+// pairs; workgroups past the boards do nothing).  The same grid at every board size: the statistics slot count below
+// is a function of N alone (gmz_conv3x3_stats_slots takes no H), so at 19x19, where one workgroup per CU is resident,
+// the workgroups past 2 CUs' worth queue behind the first ones instead of striding (only above 256 boards a launch)
 int conv3_grid(int N) {
   const long items = (2L * N + 15) / 16 * 16, cap = 2L * 2 * cu_count_conv() / 16 * 16;
   return (int)(items < cap ? items : cap);
@@ -761,12 +860,31 @@ static int check_slots(const char *fn, const double *stats, int stats_slots, int
   return 0;
 }
 
+// "6, 9, 15 or 19" from ConvSizes
+template <int... Hs>
+std::string sizes_text(SizeList<Hs...>) {
+  const int v[] = {Hs...};
+  constexpr int n = sizeof...(Hs);
+  std::string t;
+  for (int i = 0; i < n; ++i) t += (i == 0 ? "" : i == n - 1 ? " or " : ", ") + std::to_string(v[i]);
+  return t;
+}
+int bad_size(const char *fn) { return fail(std::string(fn) + ": board size must be " + sizes_text(ConvSizes{})); }
+
+// f(integral_constant<int, H>) for the H of the list, or -2 (not a supported size)
+template <typename F, int... Hs>
+int for_size(int H, SizeList<Hs...>, F &&f) {
+  int rc = -2;
+  (void)((H == Hs ? (rc = f(std::integral_constant<int, Hs>{}), true) : false) || ...);
+  return rc;
+}
+
 template <int H, typename T, bool BWD, bool PB = false, bool BNA = false>
 void launch_conv3_k(const void *x, const void *wpk, void *y, int N, const uint8_t *mask, double *stats, const void *addend,
                     const BnBwd &bn, hipStream_t st, const ActStamp &as = ActStamp{}, const BnApply &ba = BnApply{}) {
-  hipLaunchKernelGGL((k_conv3<H, T, CONV_PG, BWD, PB, BNA>), dim3(conv3_grid(N)), dim3(128 * CONV_PG), 0, st,
-                     (const uint16_t *)x, (const uint16_t *)wpk, (uint16_t *)y, N, mask, stats, (const uint16_t *)addend, bn,
-                     as, ba);
+  constexpr int PG = ConvCfg<H>::PG;
+  hipLaunchKernelGGL((k_conv3<H, T, PG, BWD, PB, BNA>), dim3(conv3_grid(N)), dim3(128 * PG), 0, st, (const uint16_t *)x,
+                     (const uint16_t *)wpk, (uint16_t *)y, N, mask, stats, (const uint16_t *)addend, bn, as, ba);
 }
 
 template <int H, typename T>
@@ -774,10 +892,15 @@ int launch_conv3(const void *x, const void *wpk, void *y, int N, const uint8_t *
                  const BnBwd &bn, hipStream_t st, bool per_board = false, const ActStamp &as = ActStamp{},
                  const BnApply &ba = BnApply{}) {
   const bool bwd = bn.x != nullptr;
+  if constexpr (!ConvCfg<H>::AB) {
+    if (bwd || as.action)
+      return fail("gmz_conv3x3: the BWD-statistics and action-stamp variants (off-by-default A/B paths) are built for "
+                  "board sizes 9 and 15 only");
+  }
   if (ba.z) launch_conv3_k<H, T, false, false, true>(x, wpk, y, N, mask, stats, addend, bn, st, as, ba);
   else if (per_board) launch_conv3_k<H, T, false, true>(x, wpk, y, N, mask, stats, addend, bn, st, as);
-  else if (bwd) launch_conv3_k<H, T, true>(x, wpk, y, N, mask, stats, addend, bn, st, as);
-  else launch_conv3_k<H, T, false>(x, wpk, y, N, mask, stats, addend, bn, st, as);
+  else if (!bwd) launch_conv3_k<H, T, false>(x, wpk, y, N, mask, stats, addend, bn, st, as);
+  else if constexpr (ConvCfg<H>::AB) launch_conv3_k<H, T, true>(x, wpk, y, N, mask, stats, addend, bn, st, as);
   GMZ_LAUNCH_CHECK();
   return 0;
 }
@@ -786,11 +909,10 @@ template <typename T>
 int conv3_dispatch(int H, const void *x, const void *wpk, void *y, int N, const uint8_t *mask, double *stats, const void *addend,
                    hipStream_t st, const BnBwd &bn = BnBwd{}, bool per_board = false, const ActStamp &as = ActStamp{},
                    const BnApply &ba = BnApply{}) {
-  switch (H) {
-    case 9: return launch_conv3<9, T>(x, wpk, y, N, mask, stats, addend, bn, st, per_board, as, ba);
-    case 15: return launch_conv3<15, T>(x, wpk, y, N, mask, stats, addend, bn, st, per_board, as, ba);
-  }
-  return fail("gmz_conv3x3: board size must be 9 or 15");
+  const int rc = for_size(H, ConvSizes{}, [&](auto h) {
+    return launch_conv3<decltype(h)::value, T>(x, wpk, y, N, mask, stats, addend, bn, st, per_board, as, ba);
+  });
+  return rc == -2 ? bad_size("gmz_conv3x3") : rc;
 }
 
 // chunks of boards: a multiple of 8 (one per XCD in each group of 24 workgroups), at most one
@@ -959,6 +1081,7 @@ GMZ_EXPORT int gmz_conv3x3_wgrad_workspace_bytes(int N, size_t *out) {
 
 static int wgrad_launch(int dtype, int H, const WgSrc &src, int N, float *dw, int64_t s0, int64_t s1, int64_t s2,
                         int64_t s3, int accumulate, void *workspace, size_t workspace_bytes, hipStream_t st) {
+  if (for_size(H, ConvSizes{}, [](auto) { return 0; }) == -2) return bad_size("gmz_conv3x3_wgrad");
   const size_t need = (size_t)wgrad_chunks(N) * 9 * CC * CC * sizeof(float);  // the partials k_conv3_wgrad writes
   if (workspace_bytes < need)
     return fail("gmz_conv3x3_wgrad: workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(N) +
@@ -966,12 +1089,10 @@ static int wgrad_launch(int dtype, int H, const WgSrc &src, int N, float *dw, in
   float *part = (float *)workspace;
   int rc;
   if (dtype == 1)
-    rc = H == 15 ? launch_wgrad<15, __half>(src, N, part, st) : H == 9 ? launch_wgrad<9, __half>(src, N, part, st) : -2;
+    rc = for_size(H, ConvSizes{}, [&](auto h) { return launch_wgrad<decltype(h)::value, __half>(src, N, part, st); });
   else if (dtype == 2)
-    rc = H == 15 ? launch_wgrad<15, __hip_bfloat16>(src, N, part, st)
-                 : H == 9 ? launch_wgrad<9, __hip_bfloat16>(src, N, part, st) : -2;
+    rc = for_size(H, ConvSizes{}, [&](auto h) { return launch_wgrad<decltype(h)::value, __hip_bfloat16>(src, N, part, st); });
   else return fail("gmz_conv3x3_wgrad: dtype must be 1 (f16) or 2 (bf16)");
-  if (rc == -2) return fail("gmz_conv3x3_wgrad: board size must be 9 or 15");
   if (rc) return rc;
   hipLaunchKernelGGL(k_conv3_wgrad_reduce, dim3((9 * CC * CC + 255) / 256), dim3(256), 0, st, (const float *)part,
                      wgrad_chunks(N), dw, (long)s0, (long)s1, (long)s2, (long)s3, accumulate);

@@ -229,7 +229,7 @@ def _conv_takes_pending(conv, z):
     """True when ``_conv3_apply(conv, y)`` of a training-mode BatchNorm output y of z's shape, dtype and layout
     runs the HIP conv that can apply the BatchNorm in its prologue (the conditions of its single-segment path)."""
     if not (DEFER_BN_APPLY and FUSED_BN and FUSED_CONV and not RELU_MASK and not FUSED_BN_BWD_STATS and z.is_cuda
-            and z.dim() == 4 and z.shape[1] == 128 and z.shape[2] == z.shape[3] and z.shape[2] in (9, 15)):
+            and z.dim() == 4 and z.shape[1] == 128 and z.shape[2] == z.shape[3] and z.shape[2] in HIP_CONV_SIZES):
         return False
     if conv.weight.shape != (128, 128, 3, 3) or conv.bias is not None:
         return False
@@ -522,6 +522,9 @@ class _Conv1x1NHWC(torch.autograd.Function):
 
 
 FUSED_CONV = True  # 128->128 3x3 convs of f16/bf16 channels-last activations run gmz_conv3x3 (HIP)
+# board sizes whose 128->128 convs take the HIP path (forward family + weight gradient: every size the engine
+# plays, gmz_conv.hip ConvSizes).  The dynamics-stem stamp (_dyn_stem_hip_ok, off by default) stays at 9 and 15.
+HIP_CONV_SIZES = (6, 9, 15, 19)
 _CONV_DTYPES = {torch.float16: 1, torch.bfloat16: 2}
 
 
@@ -894,7 +897,7 @@ def _conv3_apply(conv, x, bn=None, mask=None, link=None, segments=1):
     (row-masked) statistics, attached to the output for ``_bn_act`` (no separate reduction pass).
     ``segments`` > 1 (no_grad only): the statistics partials per board, for the segmented BatchNorm."""
     if (FUSED_CONV and x.is_cuda and x.dim() == 4 and x.shape[1] == 128 and x.shape[2] == x.shape[3]
-            and x.shape[2] in (9, 15) and conv.weight.shape == (128, 128, 3, 3) and conv.bias is None):
+            and x.shape[2] in HIP_CONV_SIZES and conv.weight.shape == (128, 128, 3, 3) and conv.bias is None):
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
         if (segments > 1 and dt in _CONV_DTYPES and x.is_contiguous(memory_format=torch.channels_last)
                 and not torch.is_grad_enabled()):

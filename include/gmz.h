@@ -365,7 +365,11 @@ int gmz_bn_eval(int dtype, int layout, const void *x_dev, const void *res_dev, i
                 void *y_dev, void *workspace_dev, size_t ws_bytes, void *stream);
 /* 3x3 convolution, 128 -> 128 channels, stride 1, padding 1, no bias (the residual-block convs of
  * network.py:30-48), on channels-last activations x[N][H*H][128] -> y[N][H*H][128]; dtype 1 = f16,
- * 2 = bf16 (activations and packed weights; f32 accumulation); H = 9 or 15.  The training step's
+ * 2 = bf16 (activations and packed weights; f32 accumulation); H = 6, 9, 15 or 19 for the forward family
+ * (gmz_conv3x3_forward, _forward_stats, _forward_board_stats, _forward_add, _forward_bnapply) and the weight
+ * gradient (gmz_conv3x3_wgrad, _wgrad_segments); H = 9 or 15 only for the two off-by-default A/B entry points
+ * (gmz_conv3x3_forward_stamp, _forward_bwdstats), which refuse 6 and 19.  Any other H fails before a launch with
+ * the list of sizes in gmz_last_error().  The training step's
  * forward convolution (loss.py:70-107 under autocast) and, with transposed packing, its input
  * gradient dx = conv(dy, W') with W'[c][o][t] = W[o][c][8 - t].
  * gmz_conv3x3_pack: f32 weight W[o][c][ky][kx] at element strides (s0, s1, s2, s3) -> packed_dev
@@ -390,7 +394,7 @@ int gmz_conv3x3_forward_board_stats(int dtype, int H, const void *x_dev, const v
  * cell's 3x3 window (tap = (a - q) + (1, 1)), table_dev f32 [9][128] = sum_c W[o][128 + c][tap] * embed[c],
  * added in f32 before the output's one rounding: table_dtype must be 0 (f32) and table_bytes 4608.  action_dev
  * int32 [N]; stats_dev / stats_slots / mask_dev as gmz_conv3x3_forward_stats (stats_dev and mask_dev may be
- * NULL).  (ABI 8; stats_slots, table_dtype, table_bytes ABI 10) */
+ * NULL).  H = 9 or 15.  (ABI 8; stats_slots, table_dtype, table_bytes ABI 10) */
 int gmz_conv3x3_forward_stamp(int dtype, int H, const void *x_dev, const void *packed_dev, void *y_dev, int N,
                               const uint8_t *mask_dev, double *stats_dev, int stats_slots, const int32_t *action_dev,
                               const void *table_dev, int table_dtype, size_t table_bytes, void *stream);
@@ -415,12 +419,14 @@ int gmz_conv3x3_forward_add(int dtype, int H, const void *x_dev, const void *pac
 /* The same convolution, also writing the BatchNorm statistics of the (rounded) output over the boards
  * whose mask_dev byte is nonzero (NULL: all): stats_dev f64 [128][slots][3] = (sum, sum of squares,
  * counted positions) per slot, slots from gmz_conv3x3_stats_slots(N) — the partials layout
- * gmz_bn_forward_stats consumes (channels-last, ns = slots).  stats_slots must equal that count (ABI 10). */
+ * gmz_bn_forward_stats consumes (channels-last, ns = slots).  stats_slots must equal that count (ABI 10), which
+ * depends on N alone, the same at every H. */
 int gmz_conv3x3_stats_slots(int N, int *slots);
 /* Weight gradient of the same convolution (the reference's autocast backward of the residual-block
  * convs): dw_dev f32 W[o][c][ky][kx] at element strides (s0..s3) = (accumulate ? dw + : ) sum over the
  * N boards of dy x^T per tap; x_dev, dy_dev channels-last [N][H*H][128] f16/bf16, 16-B aligned.
- * workspace_dev: workspace_bytes >= gmz_conv3x3_wgrad_workspace_bytes(N) bytes (per-chunk partials). */
+ * workspace_dev: workspace_bytes >= gmz_conv3x3_wgrad_workspace_bytes(N) bytes (per-chunk partials; the same at
+ * every H).  H = 6, 9, 15 or 19. */
 int gmz_conv3x3_wgrad_workspace_bytes(int N, size_t *out);
 int gmz_conv3x3_wgrad(int dtype, int H, const void *x_dev, const void *dy_dev, int N, float *dw_dev, int64_t s0,
                       int64_t s1, int64_t s2, int64_t s3, int accumulate, void *workspace_dev, size_t workspace_bytes,
@@ -440,7 +446,8 @@ int gmz_conv3x3_forward_stats(int dtype, int H, const void *x_dev, const void *p
  * also writing that BatchNorm's BACKWARD sums over the boards whose mask_dev byte is nonzero: stats_dev f64
  * [128][slots][3] = (sum dz, sum dz * xhat, counted positions), dz = y * [bn_y > 0] (relu) or y,
  * xhat = (bn_x - mean) * invstd — the partials gmz_bn_backward_stats consumes instead of its reduction pass.
- * bn_x_dev / bn_y_dev 8-B aligned; stats_slots = gmz_conv3x3_stats_slots(N).  (ABI 7; stats_slots ABI 10) */
+ * bn_x_dev / bn_y_dev 8-B aligned; stats_slots = gmz_conv3x3_stats_slots(N).  H = 9 or 15.  (ABI 7; stats_slots
+ * ABI 10) */
 int gmz_conv3x3_forward_bwdstats(int dtype, int H, const void *x_dev, const void *packed_dev, const void *addend_dev,
                                  void *y_dev, int N, const uint8_t *mask_dev, const void *bn_x_dev, const void *bn_y_dev,
                                  const float *bn_save_dev, int relu, double *stats_dev, int stats_slots, void *stream);
