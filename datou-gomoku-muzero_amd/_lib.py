@@ -100,6 +100,9 @@ _SIGS = {
     "gmz_conv3x3_forward_board_stats": ([I, I, P, P, P, I, P, P, I, P], I),
     "gmz_conv3x3_forward_stamp": ([I, I, P, P, P, I, P, P, I, P, P, I, SZ, P], I),
     "gmz_conv3x3_forward_bnapply": ([I, I, P, P, P, P, P, I, P, P, P, I, P, P, I, P], I),
+    "gmz_conv3x3_pack_split": ([P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, I, P, P], I),
+    "gmz_conv3x3_pack_split_many": ([P, I, P], I),
+    "gmz_conv3x3_forward_split": ([I, P, P, P, I, P, P, P, P, ctypes.c_float, P, I, P], I),
     "gmz_bn_forward_deferred": ([I, P, P, I, I, I, ctypes.c_float, ctypes.c_float, P, P, P, P, P, I, SZ, P, SZ, P], I),
     "gmz_bn_forward_m": ([I, I, P, P, P, I, I, I, P, P, ctypes.c_float, ctypes.c_float, P, P, P, I, P, P, P, SZ, P, P], I),
     "gmz_bn_forward_stats_m": ([I, P, P, I, I, I, P, P, ctypes.c_float, ctypes.c_float, P, P, P, I, P, P, P, I, SZ, P, P],

@@ -19,6 +19,8 @@
 // activation dtype, 8-byte stores of 4 consecutive channels.
 // Board sizes: 6, 9, 15 and 19 (ConvSizes below; per-size position groups and residency in ConvCfg<H>).  At 19x19 the
 // image is 117 KB, so one workgroup per CU; the weight gradient there stages each board in two row bands (WgLds).
+// k_conv3_split (below k_conv3) is the same convolution on float32 activations with split-f16 operands, float32-grade:
+// the target network's value trunk (gmz_conv3x3_forward_split).
 #include <type_traits>
 
 #include "gmz_common.h"
@@ -572,6 +574,270 @@ __global__ void __launch_bounds__(128 * PG, ConvCfg<H>::WG_PER_CU) k_conv3(const
   }
 }
 
+// ---- split-f16 convolution: float32 activations in, float32 out, float32-grade accuracy on the f16 MFMA pipe (gfx950
+// has no TF32 and float32 MFMA runs at 1/16 of the f16 rate): the target network's value trunk (loss.py:54-55).
+// Every float32 v is split as hi = f16(v), lo = f16((v - float(hi)) * 2^11) (the scaling keeps lo out of the f16
+// subnormals for ordinary activations; hi + lo * 2^-11 is v to max(2^-22 |v|, 2^-35)); then
+//   main = sum hi_x hi_w,  corr = sum (hi_x lo_w + lo_x hi_w),  y = main + corr * 2^-11   (all float32; lo lo dropped).
+// |v| >= 2^15 is outside the contract.  Same work item, padded image, weight-fragment ring and grid as k_conv3; the
+// packed weights are [hi fragments | lo fragments] (2 x FRAG_BYTES, k_pack_split).  ONE image, two passes per board:
+// pass 0 stages hi_x and issues, per k-step and B fragment, two MFMAs (hi_w -> main, lo_w -> corr); pass 1 re-stages
+// the image with lo_x behind a barrier and runs the 36 k-steps with hi_w into corr: 108 MFMA k-steps per board, two
+// LDS fills, no second image (19x19 fits).  global_load_lds cannot convert, so the board is staged through registers
+// (as bn_stage does), split on the way and written with 16-byte LDS stores.
+constexpr float SPLIT_SCALE = 2048.f, SPLIT_INV = 1.f / 2048.f;
+
+__device__ __forceinline__ uint16_t split_hi(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
+__device__ __forceinline__ uint16_t split_lo(float v) {
+  const _Float16 h = (_Float16)v;
+  return __builtin_bit_cast(uint16_t, (_Float16)((v - (float)h) * SPLIT_SCALE));
+}
+
+// fragment i = (t, ks, nt, l) of k_pack_conv's order, its hi half at out + 8 i and its lo half FRAG_BYTES further
+__device__ __forceinline__ void pack_split_frag(const float *__restrict__ w, long s0, long s1, long s2, long s3,
+                                                int transpose, uint16_t *__restrict__ out, int i) {
+  const int l = i & 63, nt = (i >> 6) & 7, st = i >> 9, t = st >> 2, ks = st & 3;
+  const int n = nt * 16 + (l & 15);
+  uint32_t h[4] = {0, 0, 0, 0}, lw[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = chunk_of(ks, l >> 4) * 8 + j;
+    const int o = transpose ? c : n, ci = transpose ? n : c, tt = transpose ? 8 - t : t;
+    const float v = w[o * s0 + ci * s1 + (tt / 3) * s2 + (tt % 3) * s3];
+    h[j >> 1] |= (uint32_t)split_hi(v) << (16 * (j & 1));
+    lw[j >> 1] |= (uint32_t)split_lo(v) << (16 * (j & 1));
+  }
+  *(uint4 *)(out + (size_t)i * 8) = make_uint4(h[0], h[1], h[2], h[3]);
+  *(uint4 *)(out + FRAG_BYTES / 2 + (size_t)i * 8) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+}
+
+__global__ void __launch_bounds__(256) k_pack_split(const float *__restrict__ w, long s0, long s1, long s2, long s3,
+                                                    int transpose, uint16_t *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < CKSTEPS * 8 * 64) pack_split_frag(w, s0, s1, s2, s3, transpose, out, i);
+}
+
+__global__ void __launch_bounds__(256) k_pack_split_many(const PackJob *__restrict__ jobs) {
+  const PackJob j = jobs[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < CKSTEPS * 8 * 64) pack_split_frag(j.w, j.s0, j.s1, j.s2, j.s3, j.transpose, j.out, i);
+}
+
+// The optional fused epilogue: eval-mode BatchNorm (running statistics) + residual + ReLU in k_bnl_apply's arithmetic,
+// v = (acc - mean) * (gamma * (1 / sqrtf(var + eps))) + beta, + res, max 0.  gamma = nullptr: the plain convolution.
+struct SplitBn {
+  const float *gamma, *beta, *mean, *var;
+  const float *res;  // float32 NHWC like y, or nullptr
+  float eps;
+  int relu;
+};
+
+template <int H, int PG>
+__global__ void __launch_bounds__(128 * PG, ConvCfg<H>::WG_PER_CU) k_conv3_split(const float *__restrict__ x,
+                                                                                const uint16_t *__restrict__ wpk,
+                                                                                float *__restrict__ y, int N, SplitBn bn) {
+  using I = CImg<H>;
+  using M = Mfma<__half>;
+  typedef typename M::V V;
+  constexpr int A = H * H, NPT = (A + 15) / 16;
+  constexpr int NTW = 2, PTW = (NPT + PG - 1) / PG, RD = GMZ_CONV_RD, NW = 2 * PG, NTHR = 64 * NW;
+  constexpr int PS = I::PS, RS = I::RS;
+  constexpr int NST = 2 * CKSTEPS;  // ring steps per board: pass 0's (hi_w and lo_w fragments), then pass 1's (hi_w)
+  static_assert(NST % RD == 0, "ring slots repeat per item");
+  static_assert(NTHR % 16 == 0, "a thread's chunk of every cell it stages is tid & 15");
+  // the board's last tile skips the k-steps whose tap reaches only the zero border, as in k_conv3
+  constexpr bool LAST_ONE = NPT == PG * (PTW - 1) + 1;
+  constexpr unsigned LAST_TAPS = LAST_ONE ? live_taps(H, (NPT - 1) * 16, A) : 0x1ffu;
+  __shared__ __attribute__((aligned(16))) uint8_t img[I::BYTES];
+
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int nq = w & 1, pg = w >> 1;
+  const int g4 = lane >> 4;
+  const int cg = (g4 & 1) * 8 + (g4 >> 1);
+  const int half0 = (blockIdx.x >> 3) & 1;  // the XCD-aware items of k_conv3
+  const int b0 = (int)((blockIdx.x >> 4) * 8 + (blockIdx.x & 7));
+  const int bstride = (int)(gridDim.x >> 1);
+  const int ntile0 = half0 * 4 + nq * NTW;
+
+  {  // zero the image's border cells; both stagings of every board rewrite the whole interior
+    constexpr int HP = I::HP, NBORDER = 2 * HP + 2 * H;
+    for (int i = tid; i < NBORDER * 16; i += NTHR) {
+      const int k = i >> 4, r = k - 2 * HP;
+      const int yy = k < HP ? 0 : k < 2 * HP ? HP - 1 : 1 + (r >> 1);
+      const int xx = k < HP ? k : k < 2 * HP ? k - HP : (r & 1) * (HP - 1);
+      ((uint4 *)(img + yy * RS + xx * PS))[i & 15] = make_uint4(0, 0, 0, 0);
+    }
+  }
+  auto tile_p = [&](int pt) {
+    const int p = pt * 16 + csigma16(lane & 15);
+    return (pt < NPT && p < A) ? p : A;
+  };
+  int bb[PTW];  // B-fragment read base of each tile's cell; a pad lane reads the board's last cell (never stored)
+#pragma unroll
+  for (int i = 0; i < PTW; ++i) {
+    const int p = tile_p(pg + PG * i), q = p < A ? p : A - 1;
+    bb[i] = (q / H) * RS + (q % H) * PS + cg * 16;
+  }
+  const __amdgpu_buffer_rsrc_t wrsrc =
+      __builtin_amdgcn_make_buffer_rsrc((void *)wpk, (short)0, 2 * FRAG_BYTES, 0x00020000);
+  const int wvoff = ntile0 * 1024 + lane * 16;
+  V arh[RD][NTW], arl[RD][NTW];
+  // ring step s (mod NST): pass 0 k-step s loads the hi_w and lo_w fragments, pass 1 k-step s - CKSTEPS the hi_w ones
+  auto loadA = [&](int slot, int s) {
+    const int q = s % NST, st = q < CKSTEPS ? q : q - CKSTEPS;
+#pragma unroll
+    for (int nt = 0; nt < NTW; ++nt) {
+      arh[slot][nt] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff + nt * 1024, st * 8192, 0));
+      if (q < CKSTEPS)
+        arl[slot][nt] = __builtin_bit_cast(
+            V, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff + nt * 1024, FRAG_BYTES + st * 8192, 0));
+    }
+  };
+#pragma unroll
+  for (int k = 0; k < RD - 1; ++k) loadA(k, k);
+
+  // ---- board bd -> image interior as f16 halves: thread tid takes 8-channel chunk tid & 15 of its cells (32 bytes of
+  // float32, consecutive threads consecutive addresses), U cells' loads issued before any arithmetic
+  auto stage = [&](int bd, auto lo_c) {
+    constexpr bool LO = decltype(lo_c)::value;
+    int t = tid;
+    asm volatile("" : "+v"(t));  // re-derive the cells' addresses per staging (bn_stage: hoisted, they spilled)
+    const int bch = t & 15;
+    constexpr int NCH = A * 16, NI = (NCH + NTHR - 1) / NTHR, U = 4;  // (8: spills beside the accumulators)
+    const float4 *src = (const float4 *)(x + (size_t)bd * A * CC);
+#pragma unroll
+    for (int i0 = 0; i0 < NI; i0 += U) {
+      float4 va[U], vb[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = t + (i0 + u) * NTHR;
+        if (i0 + u < NI && i < NCH) {
+          va[u] = src[2 * i];
+          vb[u] = src[2 * i + 1];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = t + (i0 + u) * NTHR;
+        if (!(i0 + u < NI && i < NCH)) continue;
+        const float f[8] = {va[u].x, va[u].y, va[u].z, va[u].w, vb[u].x, vb[u].y, vb[u].z, vb[u].w};
+        uint32_t ow[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+          const uint16_t e0 = LO ? split_lo(f[2 * h]) : split_hi(f[2 * h]);
+          const uint16_t e1 = LO ? split_lo(f[2 * h + 1]) : split_hi(f[2 * h + 1]);
+          ow[h] = (uint32_t)e0 | ((uint32_t)e1 << 16);
+        }
+        const int p = i >> 4;
+        ((uint4 *)(img + (p / H + 1) * RS + (p % H + 1) * PS))[bch] = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+      }
+    }
+  };
+
+  for (int b = b0; b < N; b += bstride) {
+    f32x4_t am[NTW][PTW], ac[NTW][PTW];  // main, corr
+#pragma unroll
+    for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+      for (int i = 0; i < PTW; ++i) am[nt][i] = ac[nt][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    auto kloop = [&](auto ntl_c, auto pass_c) {
+      constexpr int NTL = decltype(ntl_c)::value, PASS = decltype(pass_c)::value;
+      // ONE B-fragment buffer per tile (k_conv3 holds two; here the accumulators take twice the registers): tile i's
+      // fragment of the next k-step is read right after the MFMAs that consumed this one, the other tiles' MFMAs
+      // (28 in pass 0, 14 in pass 1) between that read and its use
+      V bf[NTL];
+      auto live = [&](int i, int st) {
+        const unsigned taps = (LAST_ONE && NTL == PTW && i == NTL - 1) ? LAST_TAPS : 0x1ffu;
+        return ((taps >> (st >> 2)) & 1u) != 0;
+      };
+      auto readB = [&](int i, int st) {
+        const int tap = st >> 2, ks = st & 3;
+        bf[i] = *(const V *)(img + bb[i] + (tap / 3) * RS + (tap % 3) * PS + ks * 32);
+      };
+#pragma unroll
+      for (int i = 0; i < NTL; ++i) readB(i, 0);
+#pragma unroll
+      for (int st = 0; st < CKSTEPS; ++st) {
+        constexpr int S0 = PASS * CKSTEPS;
+        loadA((S0 + st + RD - 1) % RD, S0 + st + RD - 1);
+#pragma unroll
+        for (int i = 0; i < NTL; ++i) {
+          if (live(i, st)) {
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt) {
+              if constexpr (PASS == 0) {
+                am[nt][i] = M::run(arh[(S0 + st) % RD][nt], bf[i], am[nt][i]);
+                ac[nt][i] = M::run(arl[(S0 + st) % RD][nt], bf[i], ac[nt][i]);
+              } else {
+                ac[nt][i] = M::run(arh[(S0 + st) % RD][nt], bf[i], ac[nt][i]);
+              }
+            }
+          }
+          if (st + 1 < CKSTEPS && live(i, st + 1)) readB(i, st + 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    };
+    auto pass = [&](auto pass_c) {
+      if constexpr (PTW * PG == NPT) kloop(std::integral_constant<int, PTW>{}, pass_c);
+      else if (pg + PG * (PTW - 1) < NPT) kloop(std::integral_constant<int, PTW>{}, pass_c);
+      else kloop(std::integral_constant<int, PTW - 1>{}, pass_c);
+    };
+    stage(b, std::false_type{});
+    __syncthreads();  // hi_x staged (first board: and the zeroed border)
+    pass(std::integral_constant<int, 0>{});
+    __syncthreads();  // every wave is done reading hi_x
+    stage(b, std::true_type{});
+    __syncthreads();
+    pass(std::integral_constant<int, 1>{});
+
+    // ---- epilogue: 4 consecutive output channels of one position per lane -> 16-byte store.  Its positions and
+    // channels are re-derived from an opaque copy of the lane index: hoisted out of the board loop they are spilled
+    // around the k-loops, whose accumulators leave no room for them
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int eg4 = ln >> 4, ecol = csigma16(ln & 15);
+    float *dst = y + (size_t)b * A * CC;
+    const float *rsd = bn.res ? bn.res + (size_t)b * A * CC : nullptr;
+    float mu[NTW][4], sc[NTW][4], sh[NTW][4];  // re-read per board (L1 hits) instead of kept live across the k-loops
+    if (bn.gamma) {
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = (ntile0 + nt) * 16 + eg4 * 4 + e;
+          mu[nt][e] = bn.mean[c];
+          sc[nt][e] = bn.gamma[c] * (1.0f / sqrtf(bn.var[c] + bn.eps));
+          sh[nt][e] = bn.beta[c];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < PTW; ++i) {
+      const int pt = pg + PG * i, p = pt * 16 + ecol;
+      if (pt >= NPT || p >= A) continue;
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt) {
+        const int n0 = (ntile0 + nt) * 16 + eg4 * 4;
+        f32x4_t o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = am[nt][i][e] + ac[nt][i][e] * SPLIT_INV;
+        if (bn.gamma) {
+          f32x4_t r = {0.f, 0.f, 0.f, 0.f};
+          if (rsd) r = *(const f32x4_t *)(rsd + (size_t)p * CC + n0);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float v = (o[e] - mu[nt][e]) * sc[nt][e] + sh[nt][e];
+            if (rsd) v += r[e];
+            o[e] = bn.relu ? fmaxf(v, 0.f) : v;
+          }
+        }
+        *(f32x4_t *)(dst + (size_t)p * CC + n0) = o;
+      }
+    }
+    __syncthreads();  // every wave is done reading lo_x before the next board's staging
+  }
+}
+
 // ---- weight gradient: dW[o][c][t] = sum over boards n and positions p of dy[n][p][o] * x[n][p + d(t)][c]
 // (d(t) = (t/3 - 1, t%3 - 1), zero outside the board), the GEMM M = o, N = c, K = (n, p) per tap.
 // Workgroup = (tap row ty, chunk of boards): 8 waves = 4 (32 o) x 2 (64 c), accumulating the three taps
@@ -915,6 +1181,14 @@ int conv3_dispatch(int H, const void *x, const void *wpk, void *y, int N, const 
   return rc == -2 ? bad_size("gmz_conv3x3") : rc;
 }
 
+template <int H>
+int launch_conv3_split(const float *x, const void *wpk, float *y, int N, const SplitBn &bn, hipStream_t st) {
+  constexpr int PG = ConvCfg<H>::PG;
+  hipLaunchKernelGGL((k_conv3_split<H, PG>), dim3(conv3_grid(N)), dim3(128 * PG), 0, st, x, (const uint16_t *)wpk, y, N, bn);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
 // chunks of boards: a multiple of 8 (one per XCD in each group of 24 workgroups), at most one
 // workgroup per CU
 int wgrad_chunks(int N) {
@@ -967,6 +1241,47 @@ GMZ_EXPORT int gmz_conv3x3_pack_many(int dtype, const void *jobs, int n_jobs, vo
   else return fail("gmz_conv3x3_pack_many: dtype must be 1 (f16) or 2 (bf16)");
   GMZ_LAUNCH_CHECK();
   return 0;
+}
+
+GMZ_EXPORT int gmz_conv3x3_pack_split(const float *w, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int transpose,
+                                      void *packed, void *stream) {
+  if (!w || !packed) return fail("gmz_conv3x3_pack_split: null operand");
+  if ((uintptr_t)packed & 15) return fail("gmz_conv3x3_pack_split: packed must be 16-B aligned");
+  const int n = CKSTEPS * 8 * 64;
+  hipLaunchKernelGGL(k_pack_split, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (long)s0, (long)s1,
+                     (long)s2, (long)s3, transpose, (uint16_t *)packed);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_conv3x3_pack_split_many(const void *jobs, int n_jobs, void *stream) {
+  if (!jobs || n_jobs <= 0 || n_jobs > 65535) return fail("gmz_conv3x3_pack_split_many: 1 <= n_jobs <= 65535 jobs");
+  const dim3 grid((CKSTEPS * 8 * 64 + 255) / 256, n_jobs);
+  hipLaunchKernelGGL(k_pack_split_many, grid, dim3(256), 0, (hipStream_t)stream, (const PackJob *)jobs);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_conv3x3_forward_split(int H, const float *x, const void *packed, float *y, int N, const float *gamma,
+                                         const float *beta, const float *running_mean, const float *running_var,
+                                         float eps, const float *res, int relu, void *stream) {
+  if (!x || !packed || !y) return fail("gmz_conv3x3_forward_split: null operand");
+  if (N <= 0) return fail("gmz_conv3x3_forward_split: N must be positive");
+  if (!gamma) {
+    if (beta || running_mean || running_var || res || relu)
+      return fail("gmz_conv3x3_forward_split: without gamma (the plain convolution) beta, running_mean, running_var and "
+                  "res must be NULL and relu 0");
+  } else if (!beta || !running_mean || !running_var) {
+    return fail("gmz_conv3x3_forward_split: the fused BatchNorm needs gamma, beta, running_mean and running_var");
+  }
+  if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)y | (uintptr_t)res) & 15)
+    return fail("gmz_conv3x3_forward_split: operands must be 16-B aligned");
+  if (y == x || (res && y == res)) return fail("gmz_conv3x3_forward_split: y must not alias x or res");
+  const SplitBn bn = {gamma, beta, running_mean, running_var, res, eps, relu};
+  const int rc = for_size(H, ConvSizes{}, [&](auto h) {
+    return launch_conv3_split<decltype(h)::value>(x, packed, y, N, bn, (hipStream_t)stream);
+  });
+  return rc == -2 ? bad_size("gmz_conv3x3_forward_split") : rc;
 }
 
 GMZ_EXPORT int gmz_conv3x3_stats_slots(int N, int *slots) {

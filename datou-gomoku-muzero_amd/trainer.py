@@ -526,6 +526,9 @@ FUSED_CONV = True  # 128->128 3x3 convs of f16/bf16 channels-last activations ru
 # plays, gmz_conv.hip ConvSizes).  The dynamics-stem stamp (_dyn_stem_hip_ok, off by default) stays at 9 and 15.
 HIP_CONV_SIZES = (6, 9, 15, 19)
 _CONV_DTYPES = {torch.float16: 1, torch.bfloat16: 2}
+# board sizes at which TrainNet.initial_value(split=True) takes the split-f16 kernel (those where it beats MIOpen's
+# float32 convolutions, profiles/trainer_target_split.txt)
+SPLIT_CONV_SIZES = HIP_CONV_SIZES
 
 
 def _packed_conv_weight(w, dtype, transpose, parent=None):
@@ -549,6 +552,51 @@ def _packed_conv_weight(w, dtype, transpose, parent=None):
     return out
 
 
+def split_f16(t):
+    """The split-f16 operands of a float32 tensor (gmz_conv3x3_forward_split's arithmetic, include/gmz.h), in pure
+    torch: ``hi = f16(v)`` (round to nearest even) and ``lo = f16((v - float(hi)) * 2^11)``; ``hi + lo * 2^-11`` is
+    v exactly when v has at most 22 significant bits and 2^-3 <= |v| < 2^15, within max(2^-22 |v|, 2^-35) in general.
+    |v| >= 2^15 is outside the contract."""
+    v = t.to(torch.float32)
+    hi = v.to(torch.float16)
+    lo = ((v - hi.to(torch.float32)) * 2048.0).to(torch.float16)
+    return hi, lo
+
+
+def _packed_split_weight(w):
+    """gmz_conv3x3_pack_split of ``w`` (f32 [128,128,3,3], any memory format): [hi fragments | lo fragments], cached
+    on the parameter per version counter under its own attribute (``_gmz_pack`` holds the f16/bf16 packs, which
+    _repack_stale and the tests read as 5-tuples with a dtype)."""
+    from . import _lib
+    hit = w.__dict__.get("_gmz_pack_split")
+    if hit is not None and hit[0] == w._version:
+        return hit[1]
+    out = hit[1] if hit is not None else torch.empty(294912, dtype=torch.int16, device=w.device)
+    s = w.stride()
+    _lib.check(_lib.load().gmz_conv3x3_pack_split(_lib.ptr(w.detach()), s[0], s[1], s[2], s[3], 0, _lib.ptr(out),
+                                                  _lib.stream_ptr()))
+    w.__dict__["_gmz_pack_split"] = (w._version, out, w.detach())  # (version, packed, source view)
+    return out
+
+
+def _conv3x3_split_hip(x, packed, bn=None, res=None, relu=False):
+    """gmz_conv3x3_forward_split of the float32 channels-last x; ``bn``: the eval-mode BatchNorm (+ ``res``, ReLU)
+    applied in the kernel's epilogue."""
+    from . import _lib
+    y = torch.empty_like(x, memory_format=torch.channels_last)
+    if bn is None:
+        if res is not None or relu:
+            raise ValueError("_conv3x3_split_hip: a residual or ReLU needs the BatchNorm")
+        g = b = m = v = None
+        eps = 0.0
+    else:
+        g, b, m, v, eps = bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps)
+    _lib.check(_lib.load().gmz_conv3x3_forward_split(x.shape[2], _lib.ptr(x), _lib.ptr(packed), _lib.ptr(y), x.shape[0],
+                                                     _lib.ptr(g), _lib.ptr(b), _lib.ptr(m), _lib.ptr(v), eps,
+                                                     _lib.ptr(res), int(bool(relu)), _lib.stream_ptr()))
+    return y
+
+
 _PACK_JOB = np.dtype([("w", "<u8"), ("s", "<i8", 4), ("out", "<u8"), ("transpose", "<i4"), ("pad", "<i4")])
 
 
@@ -567,10 +615,25 @@ def _repack_stale(owners, tables, prepare=False):
         for key, hit in cache.items():
             if len(hit) == 5 and hit[0] != owner._version:
                 jobs.setdefault(hit[4], []).append((owner, key, hit))
-    if not jobs:
+    split = [(o, o.__dict__["_gmz_pack_split"]) for o in owners if "_gmz_pack_split" in o.__dict__]
+    split = [(o, h) for o, h in split if h[0] != o._version]
+    if not jobs and not split:
         return 0
     capturing = torch.cuda.is_current_stream_capturing()
     n = 0
+    if split:  # the split-f16 packs (TARGET_SPLIT): one gmz_conv3x3_pack_split_many launch, same job struct
+        sig = ("split",) + tuple((h[2].data_ptr(), h[2].stride(), h[1].data_ptr()) for _, h in split)
+        table = tables.get(sig)
+        if table is None and not capturing:
+            arr = np.zeros(len(split), dtype=_PACK_JOB)
+            for i, (_, h) in enumerate(split):
+                arr[i] = (h[2].data_ptr(), h[2].stride(), h[1].data_ptr(), 0, 0)
+            table = tables[sig] = torch.from_numpy(arr.view(np.uint8)).to(split[0][1][1].device)
+        if table is not None and not prepare:
+            _lib.check(_lib.load().gmz_conv3x3_pack_split_many(_lib.ptr(table), len(split), _lib.stream_ptr()))
+            for o, h in split:
+                o.__dict__["_gmz_pack_split"] = (o._version,) + tuple(h[1:])
+            n += len(split)
     for dtype, js in jobs.items():
         sig = (dtype,) + tuple((h[2].data_ptr(), h[2].stride(), h[1].data_ptr(), h[3]) for _, _, h in js)
         table = tables.get(sig)
@@ -1419,18 +1482,45 @@ class TrainNet(nn.Module):
             return self.projection_net(h, mask)
 
     @torch.no_grad()
-    def initial_value(self, obs, f16=False):
+    def initial_value(self, obs, f16=False, split=False):
         """initial_inference's value scalar (network.py:137-143), eval mode.  ``f16``: the representation
         trunk's convolutions with f16 operands and f32 accumulation (autocast; the residual convs on the HIP
         kernels): the 10-bit mantissa the reference's float32 target forward gets from its CUDA GPU's
         default TF32 convolutions (loss.py:54-55 runs outside autocast; torch.backends.cudnn.allow_tf32 =
-        True); the prediction heads stay float32."""
+        True); the prediction heads stay float32.  ``split``: float32 activations throughout, every residual-block
+        conv with its eval BatchNorm, residual and ReLU as one split-f16 HIP launch (gmz_conv3x3_forward_split:
+        float32-grade accuracy on the f16 MFMA pipe) where the kernels cover the case (``_split_trunk_ok``); anywhere
+        else exactly the ``f16=False`` forward."""
+        if f16 and split:
+            raise ValueError("initial_value: f16 and split are different precisions of the same trunk; pick one")
         self.eval()
-        with torch.autocast("cuda", dtype=torch.float16, enabled=bool(f16) and obs.is_cuda):
-            h = self.representation(obs)
+        if split and self._split_trunk_ok(obs):
+            h = self._split_trunk(obs)
+        else:
+            with torch.autocast("cuda", dtype=torch.float16, enabled=bool(f16) and obs.is_cuda):
+                h = self.representation(obs)
         _, vl = self.prediction(h.float())  # the heads' linears in float32, as matmuls on CUDA (no TF32 default)
         c = self.cfg
         return support_to_scalar(vl.float(), c.VALUE_SUPPORT_MIN, c.VALUE_SUPPORT_MAX, c.VALUE_SUPPORT_BINS)
+
+    def _split_trunk_ok(self, obs):
+        net = self.representation_net
+        return (FUSED_CONV and obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 4 and self.channels_last
+                and obs.shape[2] == obs.shape[3] and obs.shape[2] in SPLIT_CONV_SIZES
+                and net.conv.weight.shape[0] == 128 and not torch.is_autocast_enabled("cuda")
+                and all(c.weight.shape == (128, 128, 3, 3) and c.bias is None and c.weight.dtype == torch.float32
+                        for blk in net.resblocks for c in (blk.conv1, blk.conv2)))
+
+    def _split_trunk(self, obs):
+        """The representation trunk in eval mode with the residual blocks on gmz_conv3x3_forward_split: the stem conv
+        and its BatchNorm as the float32 forward runs them, then two launches per block on float32 NHWC activations."""
+        net = self.representation_net
+        obs = obs.contiguous(memory_format=torch.channels_last)
+        h = _bn_act(net.bn, net.conv(obs)).contiguous(memory_format=torch.channels_last)
+        for blk in net.resblocks:
+            y = _conv3x3_split_hip(h, _packed_split_weight(blk.conv1.weight), blk.bn1, None, True)
+            h = _conv3x3_split_hip(y, _packed_split_weight(blk.conv2.weight), blk.bn2, h, True)
+        return h
 
 
 # ------------------------------------------------------------------------------ loss
@@ -1534,6 +1624,11 @@ CONCURRENT_FORWARD = True
 # less; |dv| <= 2e-3 vs float32 (test_target_value_f16_trunk_matches_float32).  C4 step: 36.3/36.8 vs
 # 33.5/33.1 steps/s (profiles/r04_trainer_ab_defer_target.txt).  False: float32 on MIOpen, A/B
 TARGET_F16 = True
+# the target network's value with the representation trunk's residual convs on the split-f16 HIP kernel
+# (TrainNet.initial_value split=True): float32 activations and float32-grade accuracy (each operand as two f16 halves,
+# three of the four partial products) instead of TARGET_F16's 10-bit operands or MIOpen's float32 convolutions.
+# True: this call ignores TARGET_F16.  Off by default: every existing run is unchanged
+TARGET_SPLIT = False
 # the unroll steps' cross-entropies and Barlow losses batched over the steps after the unroll (one call
 # each over the stacked [U, B, .] head outputs) instead of per step (False: per step, for A/B)
 BATCHED_LOSS = True
@@ -1832,11 +1927,11 @@ def muzero_loss(model, target_model, batch, is_weights, cfg, k=None, flip=None, 
         main = torch.cuda.current_stream(obs.device)
         side[0].wait_stream(main)
         with torch.cuda.stream(side[0]), torch.no_grad():
-            last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16)[:, 0]
+            last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16 and not TARGET_SPLIT, split=TARGET_SPLIT)[:, 0]
             z = value_targets(rew, mval, last_v, c)
     else:
         with torch.no_grad():
-            last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16)[:, 0]
+            last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16 and not TARGET_SPLIT, split=TARGET_SPLIT)[:, 0]
             z = value_targets(rew, mval, last_v, c)
     dev_type = obs.device.type
     zero = torch.zeros((), device=obs.device)
@@ -2178,7 +2273,7 @@ class Trainer:
             # takes 0.19 ms per 360-board conv (128 TFLOP/s, fp32 MFMA), so the target goes channels-last
             # too; without Find MIOpen's immediate-mode NHWC fp32 pick takes 0.51 ms and its NCHW fp32
             # Winograd 0.26 ms, so the target stays NCHW
-            if torch.backends.cudnn.benchmark or TARGET_F16:  # (f16: the HIP residual convs need NHWC)
+            if torch.backends.cudnn.benchmark or TARGET_F16 or TARGET_SPLIT:  # (the HIP residual convs need NHWC)
                 self.target = self.target.to(memory_format=torch.channels_last)
                 self.target.channels_last = True
         import torch.distributed as dist

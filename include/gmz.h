@@ -410,6 +410,31 @@ int gmz_conv3x3_forward_bnapply(int dtype, int H, const void *bn_x_dev, const vo
                                 const float *beta_dev, const float *bn_save_dev, int relu, void *bn_y_dev,
                                 const void *packed_dev, void *y_dev, int N, const uint8_t *mask_dev, double *stats_dev,
                                 int stats_slots, void *stream);
+/* The same 128 -> 128 3x3 convolution on FLOAT32 channels-last activations, x_dev f32 [N][H*H][128] -> y_dev f32
+ * [N][H*H][128], at float32-grade accuracy on the f16 MFMA pipe (gfx950 has no TF32; float32 MFMA runs at 1/16 of
+ * the f16 rate): the target network's value trunk (loss.py:54-55).  Split operands: every float32 v of x and W is
+ * taken as hi = f16(v) (round to nearest even) and lo = f16((v - float(hi)) * 2^11); hi + lo * 2^-11 is v exactly
+ * when v has at most 22 significant bits and 2^-3 <= |v| < 2^15, and within max(2^-22 |v|, 2^-35) in general.  Then
+ *   main = sum hi_x hi_w,   corr = sum (hi_x lo_w + lo_x hi_w),   y = main + corr * 2^-11,
+ * main and corr accumulated in float32 by v_mfma_f32_16x16x32_f16, the last line in float32; the lo lo term is
+ * dropped.  RANGE: |v| >= 2^15 (activations or weights) is outside the contract (hi nears the f16 maximum); so are
+ * non-finite values.  H = 6, 9, 15 or 19; any other H fails before a launch with the list of sizes.
+ * gmz_conv3x3_pack_split: f32 weight at element strides (s0..s3) -> packed_dev = [hi fragments | lo fragments],
+ *   2 x 294,912 = 589,824 bytes, 16-B aligned, each half in gmz_conv3x3_pack's fragment order; transpose = 1 packs W'.
+ * gmz_conv3x3_pack_split_many: n_jobs weights in one launch, jobs_dev as gmz_conv3x3_pack_many's (every out 589,824
+ *   bytes).
+ * gmz_conv3x3_forward_split: gamma_dev == NULL is the plain convolution, and then beta_dev, running_mean_dev,
+ *   running_var_dev and res_dev must be NULL and relu 0.  Otherwise the epilogue applies the eval-mode BatchNorm,
+ *   residual and ReLU of gmz_bn_eval in its arithmetic, per output element:
+ *   y = relu?((conv - mean[c]) * (gamma[c] * (1 / sqrtf(var[c] + eps))) + beta[c] (+ res)), res_dev f32 like y_dev
+ *   or NULL.  x_dev, packed_dev, y_dev, res_dev 16-B aligned; y_dev must not alias x_dev or res_dev; N >= 1.
+ * (Additive: ABI stays 10) */
+int gmz_conv3x3_pack_split(const float *w_dev, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int transpose,
+                           void *packed_dev, void *stream);
+int gmz_conv3x3_pack_split_many(const void *jobs_dev, int n_jobs, void *stream);
+int gmz_conv3x3_forward_split(int H, const float *x_dev, const void *packed_dev, float *y_dev, int N,
+                              const float *gamma_dev, const float *beta_dev, const float *running_mean_dev,
+                              const float *running_var_dev, float eps, const float *res_dev, int relu, void *stream);
 /* The same convolution plus an addend of the output's shape and dtype, rounded once:
  * y = round(conv(x, W) + addend).  The residual blocks' input gradient with the identity path's
  * gradient folded in (network.py:40-47 backward: d(block input) = conv1'(d conv1 out) + d(residual)),

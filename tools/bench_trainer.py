@@ -35,6 +35,8 @@ ap.add_argument("--nchw-flatten", action="store_true", help="K = 28,800 Linears 
 ap.add_argument("--no-res-fold", action="store_true", help="autograd sums the residual blocks' input gradients (trainer.FUSED_RES_GRAD off)")
 ap.add_argument("--no-defer-wgrad", action="store_true", help="3x3 weight gradients at each use (trainer.DEFER_WGRAD off)")
 ap.add_argument("--target-f32", action="store_true", help="the target network's value in float32 on MIOpen (trainer.TARGET_F16 off)")
+ap.add_argument("--target-split", action="store_true",
+                help="the target network's value trunk on the split-f16 HIP convs, float32-grade (trainer.TARGET_SPLIT on)")
 ap.add_argument("--per-step-loss", action="store_true", help="loss terms per unroll step (trainer.BATCHED_LOSS off)")
 ap.add_argument("--relu-mask", action="store_true", help="BatchNorm backward reads 1-bit ReLU masks (trainer.RELU_MASK on)")
 ap.add_argument("--hip-stem", action="store_true",
@@ -86,6 +88,7 @@ T.SEG_BN_HIP = T.SEG_BN_HIP and not a.torch_seg_bn
 T.DYN_STEM_HIP = T.DYN_STEM_HIP or a.hip_stem
 T.RELU_MASK = T.RELU_MASK or a.relu_mask
 T.TARGET_F16 = T.TARGET_F16 and not a.target_f32
+T.TARGET_SPLIT = T.TARGET_SPLIT or a.target_split
 T.DEFER_WGRAD = T.DEFER_WGRAD and not a.no_defer_wgrad
 T.DEFER_BN_APPLY = T.DEFER_BN_APPLY and not a.no_defer_bn
 T.FUSED_OPT = T.FUSED_OPT and not a.torch_opt
@@ -161,7 +164,7 @@ if rank == 0:
                       "max_memory_allocated_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
                       "defer_wgrad": T.DEFER_WGRAD, "batched_heads": T.BATCHED_HEADS, "fused_heads": T.FUSED_HEADS,
                       "dyn_stem_hip": T.DYN_STEM_HIP, "relu_mask": T.RELU_MASK,
-                      "seg_bn_hip": T.SEG_BN_HIP}))
+                      "seg_bn_hip": T.SEG_BN_HIP, "target": "split" if T.TARGET_SPLIT else "f16" if T.TARGET_F16 else "f32"}))
 if a.op_sources and rank == 0:
     # which trainer.py lines launch PyTorch's kernels (the libgmz launches have no aten op and are not counted)
     from collections import Counter
