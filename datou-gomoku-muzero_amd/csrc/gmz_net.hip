@@ -174,8 +174,10 @@ __global__ void __launch_bounds__(64 * NQ * PG) k_tower3(TowerArgs t) {
   // tiles, a tile straddling two boards (9x9: 162 positions in 11 tiles instead of 2 x 6 = 96 % fill instead of 84 %;
   // 6x6: 5 tiles instead of 6).  Each lane addresses its own position's board image, and board b's image starts
   // (b*A mod 16) 16-B slots later, so the bank slot of a position is its global index mod 16 across the board
-  // seam too: the straddling tile's B-fragment reads stay conflict-free
-  constexpr bool PACKED = NB > 1 && (NB * A + 15) / 16 < NB * NPT;
+  // seam too: the straddling tile's B-fragment reads stay conflict-free.  Every NB > 1 runs packed, also where the
+  // run saves no tile (8x8: A = 64, two boards = 8 whole tiles, no straddling tile and a zero slot offset): the gain
+  // there is the pairing itself, two boards' MFMAs per weight fragment.  6x6 and 9x9 save a tile either way.
+  constexpr bool PACKED = NB > 1;
   constexpr int NPTB = PACKED ? (NB * A + 15) / 16 : NB * NPT;
   constexpr int NW = NQ * PG, NTHR = 64 * NW;       // waves: NQ channel groups x PG position groups
   constexpr int NTW = 8 / NQ, PTW = (NPTB + PG - 1) / PG;  // n-tiles / position tiles per wave
@@ -326,7 +328,6 @@ __global__ void __launch_bounds__(64 * NQ * PG) k_tower3(TowerArgs t) {
   // group of the last tile that is one broadcast address beside the valid positions' own slots, where image offset 0
   // was a second address on a valid position's bank (a 2-way conflict on every read of that tile).  REMAP: a pad reads
   // the top border address with its slot's bank key.  pos[i] < 0 marks a pad, ~pos[i] its read base.
-  static_assert(NB == 1 || PACKED, "several boards per workgroup run as one packed position run");
   const int lastpos = bbase(NB - 1) + ((A - 1) / H) * RS + ((A - 1) % H) * PS;
   int pos[PTW];
 #pragma unroll
@@ -812,15 +813,77 @@ static int cu_count() {
   return n[dev];
 }
 
-// wave decomposition per board size.  Default: 12 waves = 4 channel quarters x 3 position groups
-// (15 tiles of 16 positions at 15x15: no idle tile, 3 waves per SIMD; RD 3 keeps it within 168
-// VGPRs).  19x19 (single LDS image, 23 tiles): 8 waves = 2 channel halves x 4 position groups.
-// NB: boards per workgroup at once — small boards (6x6, 9x9: 3 and 6 position tiles) pair up so a
-// wave's weight fragments feed 2x the MFMAs
+// the board sizes the towers are built for: tower_e, xres_bytes, check_w and the refusal text all come from this
+// list (network.BOARD_SIZES restates it; tests/test_net_sizes.py holds the two together).  20..22, which the
+// tree and game kernels accept, are not in it: 400+ positions are 25 to 31 tiles, more accumulators per wave than the
+// 19x19 decomposition, which already spills: they need a register and LDS design of their own
+template <int... Hs> struct SizeList {};
+using TowerSizes = SizeList<5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19>;
+static const char *const TOWER_SIZES_TEXT =
+    "board_size must be 5 to 19 (20 to 22, which the tree kernels accept, have no tower kernels)";
+// f(integral_constant<int, H>) for the H of the list, or -2 (not a supported size)
+template <typename F, int... Hs>
+static int for_size(int H, SizeList<Hs...>, F &&f) {
+  int rc = -2;
+  (void)((H == Hs ? (rc = f(std::integral_constant<int, Hs>{}), true) : false) || ...);
+  return rc;
+}
+
+// wave decomposition per board size: NQ channel groups x PG position groups of waves, an RD-deep weight ring, NB
+// boards per workgroup.  The unspecialised default is 6x6's: 12 waves = 4 channel quarters x 3 position groups, two
+// boards.
+// NB > 1: small boards share a workgroup as one packed position run, so a wave's weight fragments feed more MFMAs.
+// Per size: tiles = 16-position tiles per workgroup, fill = positions / (tiles x 16), split = tiles per position
+// group, LDS = the kernel's static bytes as compiled (images + bias / action tables; NB = 1: + the 4 B ticket row),
+// waves per workgroup.
+//   H  NQ PG RD NB  tiles  fill    split   LDS bytes  waves
+//   5   4  2  3  5     8   97.7 %  4|4      139,008     8   five boards: 1,024 rows are one round of 205 workgroups
+//   6   4  3  3  2     5   90.0 %  2|2|1     75,520    12
+//   7   4  2  3  2     7   87.5 %  4|3       93,952     8   last tile = two bottom-row cells: taps 6-8 skipped
+//   8   4  2  3  2     8  100.0 %  4|4      114,432     8   A = 64 = 4 tiles: pairing saves no tile, see PACKED
+//   9   4  2  3  2    11   92.0 %  6|5      136,960     8
+//  10   4  2  3  2    13   96.2 %  7|6      161,536     8   the budget's edge (163,840)
+//  11   4  2  3  1     8   94.5 %  4|4       97,284     8   from here two boards' images no longer fit
+//  12   4  2  3  1     9  100.0 %  5|4      111,620     8   last tile = the bottom row's last 16 cells: taps 6-8 skipped
+//  13   4  2  3  1    11   96.0 %  6|5      127,492     8
+//  14   4  2  3  1    13   94.2 %  7|6      144,388     8
+//  15   4  2  3  1    15   93.8 %  8|7      161,284     8   border-tile order (REMAP)
+//  16   4  2  3  1    16  100.0 %  8|8       93,444     8   from here ONE image + the residual scratch (xres)
+//  17   4  2  3  1    19   95.1 %  10|9     103,428     8   last tile = the corner cell alone: taps 0, 1, 3, 4 only
+//  18   2  4  2  1    21   96.4 %  6|5|5|5  113,924     8
+//  19   2  4  2  1    23   98.1 %  6|6|6|5  125,188     8
+// The new sizes' values are the faster of the alternatives measured per 1,024 rows, f16, 8 blocks, on one box
+// (profiles/tower_board_sizes.txt; ms):
+//   5: 4x2, 5 boards 0.122 | 4x3, 5 boards 0.136 | 4x3, 3 boards 0.259 (two rounds of workgroups, as 6x6's 0.257)
+//   7: 4x2, 2 boards 0.218 | 4x3, 2 boards 0.271 | 4x2, 3 boards 0.298 (four boards' images do not fit)
+//   8: 4x2, 2 boards 0.256 | 4x2, 1 board 0.341      10, 12, 13: 4x2 0.363, 0.549, 0.630 | 4x3 0.388, 0.606, 0.703
+//  11: 4x2 0.501 | 4x3 0.600      16, 17: 4x2 0.918, 1.070 | 2x4 0.937, 1.127      18: 2x4 1.232 | 4x2 1.235, more scratch
+// so two position groups (a weight fragment feeds 4..10 MFMAs per wave and is fetched by two waves per channel
+// quarter, the 9x9 and 15x15 results) everywhere but 18x18.  17x17's 10 | 9 tiles per wave spill 80..112 B per lane
+// (19x19: 76..116) and are still the faster split; 18x18's 11 | 10 spill more than its 2 x 4 (20..88 B) for no gain.
+// (Three of the alternatives ran on a second box; their figures are scaled by the ratio of the two boxes' 15x15
+// times, 1.047.)
+// B-fragment bank map (Img3: RS / 16 = 17 H + 32 = H mod 16 at every H, PS / 16 = 1 mod 16): modelled per hardware
+// lane group for every tile, tap and k-step by tools/tower_bank_model.py.  Conflict-free at every size, H = 16 and the
+// packed seams of 5 (five boards), 7, 8 and 10 included, except the LAST tile at 11, 13 and 19 (9 valid positions +
+// 7 pads): the pads' read of lastpos + 128 B lands on the first valid position's slot, a 2-way conflict on that
+// tile's reads (1 tile of 8, 11 and 23).  19x19 has always run so; its cost is inside the times above, which meet
+// the smaller-board-is-not-slower condition, and the pad address is left alone so the 19x19 kernels do not change.
 template <int H> struct TowerCfg { static constexpr int NQ = 4, PG = 3, RD = 3, NB = 2; };
+template <> struct TowerCfg<5> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 5; };
+template <> struct TowerCfg<7> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 2; };
+template <> struct TowerCfg<8> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 2; };
 // 9x9, two boards: 8 waves x 6 tiles beat 12 x 4 (0.340 vs 0.365 ms per 1024 rows, measured)
 template <> struct TowerCfg<9> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 2; };
+template <> struct TowerCfg<10> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 2; };
+template <> struct TowerCfg<11> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };
+template <> struct TowerCfg<12> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };
+template <> struct TowerCfg<13> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };
+template <> struct TowerCfg<14> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };
 template <> struct TowerCfg<15> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };  // 8 tiles | 7 tiles
+template <> struct TowerCfg<16> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };
+template <> struct TowerCfg<17> { static constexpr int NQ = 4, PG = 2, RD = 3, NB = 1; };
+template <> struct TowerCfg<18> { static constexpr int NQ = 2, PG = 4, RD = 2, NB = 1; };
 template <> struct TowerCfg<19> { static constexpr int NQ = 2, PG = 4, RD = 2, NB = 1; };
 
 // bytes of k_tower3's per-workgroup residual scratch (single-image boards only)
@@ -832,13 +895,9 @@ static constexpr size_t tower_xres_bytes() {
   return one ? (size_t)T::NQ * T::PG * (8 / T::NQ) * ptw * 64 * 8 : 0;
 }
 static size_t xres_bytes(int H) {
-  switch (H) {
-    case 6: return tower_xres_bytes<6>();
-    case 9: return tower_xres_bytes<9>();
-    case 15: return tower_xres_bytes<15>();
-    case 19: return tower_xres_bytes<19>();
-    default: return 0;
-  }
+  size_t n = 0;
+  for_size(H, TowerSizes{}, [&](auto h) { return (n = tower_xres_bytes<decltype(h)::value>(), 0); });
+  return n;
 }
 
 // tower launch generations (k_tower3's ticket word): increasing across every launch of the process, from 1
@@ -861,13 +920,11 @@ static int launch_tower(const TowerArgs &a, hipStream_t s) {
 
 template <typename E>
 static int tower_e(int H, bool dyn, const TowerArgs &a, hipStream_t s) {
-  switch (H) {
-    case 6: return dyn ? launch_tower<6, true, E>(a, s) : launch_tower<6, false, E>(a, s);
-    case 9: return dyn ? launch_tower<9, true, E>(a, s) : launch_tower<9, false, E>(a, s);
-    case 15: return dyn ? launch_tower<15, true, E>(a, s) : launch_tower<15, false, E>(a, s);
-    case 19: return dyn ? launch_tower<19, true, E>(a, s) : launch_tower<19, false, E>(a, s);
-    default: return fail("gmz_net: board_size must be one of 6, 9, 15, 19");
-  }
+  const int rc = for_size(H, TowerSizes{}, [&](auto h) {
+    constexpr int HH = decltype(h)::value;
+    return dyn ? launch_tower<HH, true, E>(a, s) : launch_tower<HH, false, E>(a, s);
+  });
+  return rc == -2 ? fail(std::string("gmz_net: ") + TOWER_SIZES_TEXT) : rc;
 }
 static int tower(const gmz_net_weights *w, bool dyn, const TowerArgs &a0, hipStream_t s) {
   TowerArgs a = a0;
@@ -905,8 +962,8 @@ static int check_w(const gmz_net_weights *w) {
   if (!w) return fail("gmz_net: null weights");
   if (w->channels != C) return fail("gmz_net: channels must be 128");
   if (w->head_hidden != 64) return fail("gmz_net: head_hidden must be 64");
-  if (w->board_size != 6 && w->board_size != 9 && w->board_size != 15 && w->board_size != 19)
-    return fail("gmz_net: board_size must be 6, 9, 15 or 19");
+  if (for_size(w->board_size, TowerSizes{}, [](auto) { return 0; }) == -2)
+    return fail(std::string("gmz_net: ") + TOWER_SIZES_TEXT);
   if (w->dtype != GMZ_NET_F16 && w->dtype != GMZ_NET_BF16) return fail("gmz_net: dtype must be GMZ_NET_F16 or GMZ_NET_BF16");
   return 0;
 }

@@ -31,6 +31,9 @@ from .config import from_any
 
 EPS = 1e-4
 C = 128
+# board sizes the inference towers are built for (csrc/gmz_net.hip TowerSizes; tests/test_net_sizes.py checks
+# that the two lists accept the same sizes).  20..22, which the tree and game kernels accept, have no tower.
+BOARD_SIZES = tuple(range(5, 20))
 
 
 class NetWeights(ctypes.Structure):
@@ -232,8 +235,9 @@ class GomokuNetHip:
         self.precision = precision
         self.cfg = from_any(cfg, **overrides)
         c = self.cfg
-        if c.NUM_FILTERS != C or c.HEAD_HIDDEN_DIM != 64 or c.BOARD_SIZE not in (6, 9, 15, 19):
-            raise ValueError("GomokuNetHip: kernels support NUM_FILTERS=128, HEAD_HIDDEN_DIM=64, BOARD_SIZE 6/9/15/19")
+        if c.NUM_FILTERS != C or c.HEAD_HIDDEN_DIM != 64 or c.BOARD_SIZE not in BOARD_SIZES:
+            raise ValueError("GomokuNetHip: kernels support NUM_FILTERS=128, HEAD_HIDDEN_DIM=64, BOARD_SIZE %d to %d "
+                             "(20 to 22 run in the tree kernels only)" % (BOARD_SIZES[0], BOARD_SIZES[-1]))
         self.device = torch.device(device)
         self.A = c.ACTION_SPACE_SIZE
         self.lib = _lib.load()

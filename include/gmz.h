@@ -208,7 +208,7 @@ int gmz_hashnet_recurrent(uint32_t *hid_pool_dev, const int32_t *in_slot_dev, co
 /* Device pointers to the packed inference weights (datou-gomoku-muzero_amd/network.py:pack_weights
  * builds them from a reference state_dict: BatchNorm folded, 16-bit (`dtype`) conv weights in MFMA fragment
  * order).  Kernels are specialised for channels == 128, head_hidden == 64, 3 support bins,
- * board_size in {6, 9, 15, 19}. */
+ * board_size 5 to 19 (20 to 22, which the engine entry points take, are refused by every gmz_net_* call). */
 typedef struct gmz_net_weights {
   int32_t board_size, channels, blocks, head_hidden;
   const uint16_t *repr_stem_w;  /* e16  [8][64][8]       conv 3->C, k = tap*3 + c (27 -> 32)      */
