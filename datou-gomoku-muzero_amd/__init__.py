@@ -6,6 +6,8 @@ Drop-in for the reference's self-play hot path:
   * ``engine.BatchedSelfPlayEngine`` — G games per GPU, search + play as HIP kernels;
   * ``worker.gpu_selfplay_worker`` — process target emitting the messages of workers.py:129-241.
 
+Beyond the reference: ``arena.Arena`` — one network against another on the GPU (paired openings, Elo).
+
 Native code: ``csrc/`` → ``libgmz.so`` (C ABI declared in include/gmz.h), loaded by ``_lib``.
 """
 from .config import GmzConfig  # noqa: F401

@@ -905,10 +905,23 @@ __device__ int select_nonroot_cl(const Dev &D, const uint64_t (&lg)[NJ], int lm,
   return a;
 }
 
+// Gumbel(0, 1) sample of (seed, move counter, game key, action): the device noise of k_begin_move and
+// k_gumbel_keyed (mcts.py:312, np.random.gumbel)
+__device__ __forceinline__ double gumbel_noise(uint64_t seed, uint32_t counter, uint32_t key, int a) {
+  const uint32_t h1 = mix32((uint32_t)seed ^ mix32(counter * 0x9E3779B1u + key * 0x85EBCA77u));
+  const uint32_t h2 = mix32(h1 ^ mix32((uint32_t)a + 0x68E31DA4u) ^ (uint32_t)(seed >> 32));
+  const uint32_t h3 = mix32(h2 + 0x1B873593u);
+  const uint64_t bits = ((uint64_t)h2 << 21) ^ (uint64_t)h3;  // 53 random bits
+  double u = (double)(bits & ((1ull << 53) - 1)) * 0x1.0p-53;
+  if (u <= 0.0) u = 0x1.0p-53;
+  return -log(-log(1.0 - u));
+}
+
 // ------------------------------------------------------------------------------------------
 template <int NJ>
 __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restrict__ gumbel_in, uint64_t seed,
-                                                    uint32_t counter, float *__restrict__ obs) {
+                                                    uint32_t counter, float *__restrict__ obs,
+                                                    const uint8_t *__restrict__ active) {
   __shared__ int16_t table[4][2048];
   __shared__ int16_t oldk[4][512];
   const int w = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
@@ -918,11 +931,14 @@ __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restr
   const int8_t *b = D.boards + (size_t)g * A;
   const int8_t pl = D.players[g];
   const int lm = D.last_moves[g];
+  // an inactive game (gmz_engine_set_active) has no legal move: no search, action -1
+  // (active: gmz_engine_set_active's mask, uint8[G], nullptr = every game)
+  const bool live = !active || active[g];
   int nl = 0;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int a = lane + WAVE * j;
-    const bool ok = a < A && b[a] == 0;
+    const bool ok = live && a < A && b[a] == 0;
     const uint64_t bal = __ballot(ok);
     if (lane == 0) D.legal[(size_t)g * gmz::NJ + j] = bal;
     nl += __popcll(bal);
@@ -945,13 +961,7 @@ __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restr
     if (gumbel_in) {
       gv = gumbel_in[(size_t)g * A + a];
     } else {
-      const uint32_t h1 = mix32((uint32_t)seed ^ mix32(counter * 0x9E3779B1u + (uint32_t)(g + D.game_offset) * 0x85EBCA77u));
-      const uint32_t h2 = mix32(h1 ^ mix32((uint32_t)a + 0x68E31DA4u) ^ (uint32_t)(seed >> 32));
-      const uint32_t h3 = mix32(h2 + 0x1B873593u);
-      const uint64_t bits = ((uint64_t)h2 << 21) ^ (uint64_t)h3;  // 53 random bits
-      double u = (double)(bits & ((1ull << 53) - 1)) * 0x1.0p-53;
-      if (u <= 0.0) u = 0x1.0p-53;
-      gv = -log(-log(1.0 - u));
+      gv = gumbel_noise(seed, counter, (uint32_t)(g + D.game_offset), a);
     }
     gm[a] = gv;
   }
@@ -961,7 +971,7 @@ __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restr
     int mask = 7, fill = 0;
     for (int i = 0; i < 8; ++i) T[i] = -1;
     for (int a = 0; a < A; ++a) {
-      if (b[a] != 0) continue;
+      if (b[a] != 0 || !live) continue;
       // set_add_entry probing
       unsigned perturb = (unsigned)a, i = (unsigned)a & mask;
       for (;;) {
@@ -1808,6 +1818,76 @@ __global__ void k_play_engine(Dev D, int n_in_row, const int32_t *__restrict__ a
            actions[g], status + g, reset_finished);
 }
 
+// k_play_engine (no reset) + the arena's bookkeeping (gmz_engine_play_refill): one thread per slot
+struct RefillArgs {
+  const int32_t *actions;
+  int8_t *status;
+  const int8_t *book_boards, *book_players;
+  const int32_t *book_last, *book_counts;
+  int n_openings, next_net;
+  int32_t *tickets, *slot_game;
+  uint32_t *slot_key, *slot_ply;
+  int32_t *n_legal;
+  int8_t *res_winner;
+  int32_t *res_length;
+  int16_t *res_moves;
+  int moves_stride;
+  int32_t *finished;
+  uint8_t *active;  // the engine's mask buffer
+};
+
+__global__ void k_play_refill(Dev D, int n_in_row, RefillArgs R) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= D.G) return;
+  const int A = D.A;
+  int8_t *b = D.boards + (size_t)g * A;
+  const int act = R.actions[g];
+  int8_t st;
+  play_one(b, D.size, n_in_row, D.players + g, D.last_moves + g, D.move_counts + g, act, &st, 0);
+  R.status[g] = st;
+  int id = R.slot_game[g];
+  if (st != 3 && id >= 0) {
+    const uint32_t ply = R.slot_ply[g];
+    if (R.res_moves && (int)ply < R.moves_stride) R.res_moves[(size_t)id * R.moves_stride + ply] = (int16_t)act;
+    R.slot_ply[g] = ply + 1;
+    if (st != 2) {
+      R.res_winner[id] = st;
+      R.res_length[id] = (int32_t)(ply + 1);
+      atomicAdd(R.finished, 1);
+      id = -1;
+      R.slot_game[g] = -1;
+    }
+  }
+  if (id < 0) {  // idle: the next opening of the network on turn, if one is left
+    int32_t *tk = R.tickets + R.next_net;
+    int t = R.n_openings;
+    if (__atomic_load_n(tk, __ATOMIC_RELAXED) < R.n_openings) t = atomicAdd(tk, 1);
+    if (t < R.n_openings) {
+      const int8_t *ob = R.book_boards + (size_t)t * A;
+      for (int i = 0; i < A; ++i) b[i] = ob[i];
+      D.players[g] = R.book_players[t];
+      D.last_moves[g] = R.book_last[t];
+      D.move_counts[g] = R.book_counts[t];
+      R.slot_game[g] = 2 * t + R.next_net;
+      R.slot_key[g] = (uint32_t)t;
+      R.slot_ply[g] = 0;
+      R.active[g] = 1;
+      id = 0;
+    } else {
+      R.active[g] = 0;
+    }
+  }
+  R.n_legal[g] = id >= 0 ? A - D.move_counts[g] : 0;
+}
+
+__global__ void k_gumbel_keyed(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ plies, uint64_t seed,
+                               int G, int A, double *__restrict__ out) {
+  const int g = blockIdx.y;
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G || a >= A) return;
+  out[(size_t)g * A + a] = gumbel_noise(seed, plies[g], keys[g], a);
+}
+
 __global__ void k_reset_games(Dev D, const uint8_t *__restrict__ mask) {
   const int g = blockIdx.y;
   if (g >= D.G || (mask && !mask[g])) return;
@@ -1870,6 +1950,8 @@ struct gmz_engine {
   int n_in_row;
   uint32_t counter;
   int es_waves;  // resident waves of the engine's k_expand_select variant (0: not measured yet)
+  uint8_t *active_buf;    // [G] storage of the active mask (gmz_engine_set_active, gmz_engine_play_refill)
+  const uint8_t *active;  // active_buf once a mask is set, nullptr = every game is searched (k_begin_move)
   void *bufs[32];
   int nbufs;
 };
@@ -1937,6 +2019,7 @@ GMZ_EXPORT int gmz_engine_create(const gmz_engine_cfg *cfg, gmz_engine **out) {
   rc |= dalloc(e, &D.players, G);
   rc |= dalloc(e, &D.last_moves, G);
   rc |= dalloc(e, &D.move_counts, G);
+  rc |= dalloc(e, &e->active_buf, G);
   if (rc) {
     gmz_engine_destroy(e);
     return -1;
@@ -2100,7 +2183,7 @@ static int launch_expand_select_nj(gmz_engine *e, hipStream_t s, const float *lo
 GMZ_EXPORT int gmz_engine_begin_move(gmz_engine *e, const double *gumbel, uint64_t seed, float *obs, void *stream) {
   if (!e || !obs) return fail("gmz_engine_begin_move: null argument");
   const uint32_t ctr = e->counter++;
-  GMZ_LAUNCH_NJ(k_begin_move, e, stream, e->D, gumbel, seed, ctr, obs);
+  GMZ_LAUNCH_NJ(k_begin_move, e, stream, e->D, gumbel, seed, ctr, obs, e->active);
   return 0;
 }
 
@@ -2202,6 +2285,73 @@ GMZ_EXPORT int gmz_engine_play(gmz_engine *e, const int32_t *action, int8_t *sta
   if (!e || !action || !status) return fail("gmz_engine_play: null argument");
   hipLaunchKernelGGL(k_play_engine, dim3((e->D.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->D, e->n_in_row,
                      action, status, reset_finished);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_engine_set_active(gmz_engine *e, const uint8_t *mask_dev, void *stream) {
+  if (!e) return fail("gmz_engine_set_active: null engine");
+  if (!mask_dev) {
+    e->active = nullptr;
+    return 0;
+  }
+  GMZ_HIP(hipMemcpyAsync(e->active_buf, mask_dev, (size_t)e->D.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  e->active = e->active_buf;
+  return 0;
+}
+
+GMZ_EXPORT int gmz_engine_set_simulations(gmz_engine *e, int num_simulations) {
+  if (!e) return fail("gmz_engine_set_simulations: null engine");
+  if (num_simulations < 1 || num_simulations > e->cfg.num_simulations)
+    return fail("gmz_engine_set_simulations: need 1 <= num_simulations <= " + std::to_string(e->cfg.num_simulations) +
+                " (the engine's budget at creation)");
+  e->D.n_sims = num_simulations;
+  return 0;
+}
+
+GMZ_EXPORT int gmz_engine_play_refill(gmz_engine *e, const int32_t *action, int8_t *status, const int8_t *book_boards,
+                                      const int8_t *book_players, const int32_t *book_last, const int32_t *book_counts,
+                                      int n_openings, int32_t *tickets, int next_net, int32_t *slot_game,
+                                      uint32_t *slot_key, uint32_t *slot_ply, int32_t *n_legal, int slot_capacity,
+                                      int8_t *res_winner, int32_t *res_length, int16_t *res_moves, int moves_stride,
+                                      int res_capacity, int32_t *finished, void *stream) {
+  // everything that does not need the engine first: a bad call is refused whatever the handle
+  if (!e || !action || !status) return fail("gmz_engine_play_refill: null engine, action or status");
+  if (!book_boards || !book_players || !book_last || !book_counts) return fail("gmz_engine_play_refill: null book array");
+  if (!tickets || !finished) return fail("gmz_engine_play_refill: null ticket or finished counter");
+  if (!slot_game || !slot_key || !slot_ply || !n_legal) return fail("gmz_engine_play_refill: null slot array");
+  if (!res_winner || !res_length) return fail("gmz_engine_play_refill: null result array");
+  if (n_openings < 1 || n_openings > (1 << 29)) return fail("gmz_engine_play_refill: n_openings must be in [1, 2^29]");
+  if (next_net != 0 && next_net != 1) return fail("gmz_engine_play_refill: next_net must be 0 or 1");
+  if (res_capacity < 2 * n_openings)
+    return fail("gmz_engine_play_refill: result arrays hold " + std::to_string(res_capacity) + " games, the match has " +
+                std::to_string(2 * n_openings));
+  if (slot_capacity < 1) return fail("gmz_engine_play_refill: slot_capacity must be >= the engine's games");
+  if (res_moves && moves_stride < 1) return fail("gmz_engine_play_refill: moves_stride must be >= board_size^2");
+  if (slot_capacity < e->D.G)
+    return fail("gmz_engine_play_refill: slot arrays hold " + std::to_string(slot_capacity) + " slots, the engine has " +
+                std::to_string(e->D.G));
+  if (res_moves && moves_stride < e->D.A)
+    return fail("gmz_engine_play_refill: moves_stride " + std::to_string(moves_stride) + " < board_size^2 = " +
+                std::to_string(e->D.A));
+  RefillArgs R{action, status, book_boards, book_players, book_last, book_counts, n_openings, next_net, tickets,
+               slot_game, slot_key, slot_ply, n_legal, res_winner, res_length, res_moves, moves_stride, finished,
+               e->active_buf};
+  hipLaunchKernelGGL(k_play_refill, dim3((e->D.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->D, e->n_in_row, R);
+  GMZ_LAUNCH_CHECK();
+  e->active = e->active_buf;  // every slot's byte was written by the launch
+  return 0;
+}
+
+GMZ_EXPORT int gmz_gumbel_keyed(const uint32_t *keys, const uint32_t *plies, uint64_t seed, int G, int A, double *out,
+                                size_t out_bytes, void *stream) {
+  if (!keys || !plies || !out) return fail("gmz_gumbel_keyed: null argument");
+  if (G < 1 || A < 1 || A > MAX_A) return fail("gmz_gumbel_keyed: need G >= 1 and 1 <= A <= 512");
+  if (out_bytes < (size_t)G * A * sizeof(double))
+    return fail("gmz_gumbel_keyed: out holds " + std::to_string(out_bytes) + " bytes, G * A * 8 = " +
+                std::to_string((size_t)G * A * sizeof(double)));
+  hipLaunchKernelGGL(k_gumbel_keyed, dim3((A + 255) / 256, G), dim3(256), 0, (hipStream_t)stream, keys, plies, seed, G, A,
+                     out);
   GMZ_LAUNCH_CHECK();
   return 0;
 }

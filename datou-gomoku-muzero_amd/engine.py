@@ -106,6 +106,8 @@ class BatchedSelfPlayEngine:
         # hidden-state slots per game by legal-move count (gmz_engine_set_hidden_bases): MuZero creates one
         # node per wave (mcts.py:320-350), so a game needs waves(L) + 2 slots, not num_simulations + 2
         self._slot_need = slot_need_table(self.ecfg, A, self.mode, self.lib)
+        self._run_cfg = self.ecfg  # the budget the searches run with (set_simulations)
+        self._sims_tables = {c.NUM_SIMULATIONS: (self.ecfg, self._slot_need)}
         self.net = net if net is not None else HashNetBackend(G * int(self._slot_need[A]), A, device)
         f32, i32 = torch.float32, torch.int32
         self.obs = torch.zeros(G, 3, c.BOARD_SIZE, c.BOARD_SIZE, dtype=f32, device=dev)
@@ -135,6 +137,12 @@ class BatchedSelfPlayEngine:
         self._err_host = torch.zeros(1, dtype=i32).pin_memory()  # the engine's error word, copied with each status
         self._status_event = None
         self._n_legal = np.full(G, A, dtype=np.int32)
+        self._active = None  # host copy of set_active's mask (None: every game is searched)
+        self._refill = None  # play_refill's slot arrays and pinned read-back buffers (arena)
+        self._refill_pending = False
+        self.finished_seen = 0  # the match's finished-games counter as of the last status read (play_refill)
+        self.moves_played = 0   # moves counted from the statuses read after play_refill calls
+        self._hb_net = None     # the backend whose pool the last placement was checked against
         self._last_reset = True
         self.waves_last = 0
         self.tree_timer = None  # optional network.KernelTimer around the fused expand/backup+select launches
@@ -183,6 +191,39 @@ class BatchedSelfPlayEngine:
         self._n_legal = (A - nz.numpy()).astype(np.int32)
         self._status_event = None
 
+    def set_active(self, mask=None):
+        """Search only the games whose ``mask`` byte is nonzero (uint8/bool [G], host array; None: every game,
+        the default).  An inactive game joins no wave and adds nothing to the tree counters; search() gives it
+        action -1 and play() leaves it untouched with status 3.  The other games are searched exactly as
+        without a mask (gmz_engine_set_active).  Holds from the next search on."""
+        if mask is None:
+            self._active = None
+            check(self.lib.gmz_engine_set_active(self.handle, None, self._stream()))
+            return
+        m = np.ascontiguousarray(np.asarray(mask).reshape(self.G) != 0)
+        d = torch.as_tensor(m.astype(np.uint8)).to(self.device)
+        check(self.lib.gmz_engine_set_active(self.handle, ptr(d), self._stream()))
+        d.record_stream(torch.cuda.current_stream(self.device))
+        self._active = m
+
+    def set_simulations(self, n):
+        """Simulations per search from the next search on, 1 <= n <= the NUM_SIMULATIONS the engine was built
+        with: the searches are then those of an engine built with n (gmz_engine_set_simulations).  Between
+        moves only."""
+        n = int(n)
+        if n == self._run_cfg.num_simulations:
+            return
+        check(self.lib.gmz_engine_set_simulations(self.handle, n))
+        if n not in self._sims_tables:
+            ec = _lib.EngineCfg.from_buffer_copy(self.ecfg)
+            ec.num_simulations = n
+            self._sims_tables[n] = (ec, slot_need_table(ec, self.A, self.mode, self.lib))
+        self._run_cfg, self._slot_need = self._sims_tables[n]
+
+    def _legal_counts(self):
+        """The legal-move count each game's coming search sees: 0 for a game outside the active mask."""
+        return self._n_legal if self._active is None else np.where(self._active, self._n_legal, 0).astype(np.int32)
+
     def reset_games(self, mask=None):
         m = None
         if mask is not None:
@@ -200,6 +241,14 @@ class BatchedSelfPlayEngine:
             if err:  # a void search must not reach self-play records or the replay buffer
                 raise GmzError("engine error bits 0x%x after the last move: a search passed its game's hidden-state "
                                "slot budget, so that game's search result is void (gmz_engine_errors)" % err)
+            if self._refill_pending:  # play_refill: the slots' legal counts come back exact (0 = idle slot)
+                r = self._refill
+                self._n_legal[:] = r["host"].numpy()[:self.G]
+                self.finished_seen = int(r["host"][self.G])
+                self.moves_played += int((self._status_host.numpy() != 3).sum())
+                self._refill_pending = False
+                self._status_event = None
+                return
             st = self._status_host.numpy()
             ended = st != 2
             played = st != 3
@@ -217,20 +266,26 @@ class BatchedSelfPlayEngine:
         been read yet it is the last search's L - 1, or A for a game that ended and restarted: the larger
         need of the two is taken.  The bases change only when a game's need does (late-game positions with
         fewer than NUM_TOP_ACTIONS legal moves); then they are copied to the device on the search's stream."""
-        nl = self._n_legal
+        nl = self._legal_counts()
         need = self._slot_need[np.clip(nl, 0, self.A)]
-        if self._status_event is not None:  # a move was played since nl was read
-            need = np.maximum(self._slot_need[np.clip(nl - 1, 0, self.A)], self._slot_need[self.A])
+        if self._status_event is not None:  # a move was played since nl was read (play_refill: or a slot was
+            # refilled from an opening with >= NUM_TOP_ACTIONS legal cells, whose need is that of the empty board)
+            need = np.maximum(self._slot_need[np.clip(self._n_legal - 1, 0, self.A)], self._slot_need[self.A])
         base = np.zeros(self.G, np.int64)
         np.cumsum(need[:-1], out=base[1:])
         total = int(base[-1] + need[-1])
         key = np.concatenate([base, need])
         if self._hb_last is not None and np.array_equal(key, self._hb_last):
+            if self._hb_net is not self.net:  # the backend was changed between moves: its pool must hold the slots
+                if hasattr(self.net, "ensure_slots"):
+                    self.net.ensure_slots(total, stream)
+                self._hb_net = self.net
             return
         if total >= 2 ** 31:
             raise ValueError("hidden-state pool: %d slots exceed the int32 slot index" % total)
         if hasattr(self.net, "ensure_slots"):
             self.net.ensure_slots(total, stream)
+        self._hb_net = self.net
         i = self._hb_flip
         self._hb_flip ^= 1
         if self._hb_events[i] is not None:
@@ -258,8 +313,8 @@ class BatchedSelfPlayEngine:
 
     def waves_needed(self):
         out = ctypes.c_int32()
-        nl = np.ascontiguousarray(self._n_legal, dtype=np.int32)
-        check(self.lib.gmz_engine_waves_for_legal(ctypes.byref(self.ecfg), nl.ctypes.data_as(ctypes.c_void_p),
+        nl = np.ascontiguousarray(self._legal_counts(), dtype=np.int32)
+        check(self.lib.gmz_engine_waves_for_legal(ctypes.byref(self._run_cfg), nl.ctypes.data_as(ctypes.c_void_p),
                                                   self.G, ctypes.byref(out)))
         return out.value
 
@@ -324,6 +379,52 @@ class BatchedSelfPlayEngine:
         self._status_event = ev
         self._last_reset = bool(reset_finished)
         return self.status
+
+    def play_refill(self, match, next_net, action=None, stream=None):
+        """play(reset_finished=False) plus an arena's bookkeeping in one launch (gmz_engine_play_refill):
+        finished games go to ``match``'s result arrays, idle slots start the next opening of network
+        ``next_net`` (the one that moves next on this engine) or go inactive.  ``match``: a MatchBuffers,
+        shared by the engines of one match.  The slots' legal counts, the status and the match's
+        finished-games counter come back through the pinned buffers and the event play() uses, and are read
+        at the next search (one ply behind); no host synchronisation here.  Call it from the torch stream
+        context of ``stream``.  The first call (``action`` = -1 everywhere) fills the slots."""
+        s = self._stream(stream)
+        G, dev = self.G, self.device
+        if match.A != self.A:
+            raise ValueError("play_refill: the book's boards are not this engine's size")
+        r = self._refill
+        if r is None:
+            i32 = torch.int32
+            r = self._refill = dict(
+                game=torch.full((G,), -1, dtype=i32, device=dev), key=torch.zeros(G, dtype=i32, device=dev),
+                ply=torch.zeros(G, dtype=i32, device=dev),
+                back=torch.zeros(G + 1, dtype=i32, device=dev),  # legal counts [G], then the finished counter
+                host=torch.zeros(G + 1, dtype=i32).pin_memory())
+        a = self.action if action is None else torch.as_tensor(action, dtype=torch.int32).to(dev)
+        m = match
+        check(self.lib.gmz_engine_play_refill(
+            self.handle, ptr(a), ptr(self.status), ptr(m.boards), ptr(m.players), ptr(m.last_moves), ptr(m.move_counts),
+            m.n_openings, ptr(m.tickets), int(next_net), ptr(r["game"]), ptr(r["key"]), ptr(r["ply"]), ptr(r["back"]), G,
+            ptr(m.winner), ptr(m.length), ptr(m.moves), m.A, m.winner.numel(), ptr(m.finished), s))
+        r["back"][G:].copy_(m.finished, non_blocking=True)
+        r["host"].copy_(r["back"], non_blocking=True)
+        self._status_host.copy_(self.status, non_blocking=True)
+        check(self.lib.gmz_engine_errors_async(self.handle, ptr(self._err_host), s))
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream() if stream is None else stream)
+        self._status_event = ev
+        self._refill_pending = True
+        self._active = None  # the device mask is the slots' own now; idle slots report 0 legal cells
+        self._last_reset = False
+        return self.status
+
+    def keyed_gumbel(self, out, stream=None):
+        """The arena's noise for the coming search into ``out`` f64[G,A]: row g from (seed, the slot's opening,
+        its game's ply) alone (gmz_gumbel_keyed with play_refill's slot arrays)."""
+        r = self._refill
+        check(self.lib.gmz_gumbel_keyed(ptr(r["key"]), ptr(r["ply"]), self.seed, self.G, self.A, ptr(out),
+                                        _lib.nbytes(out), self._stream(stream)))
+        return out
 
     def winning_scan(self, boards, players, action=None, counters=None, stream=None):
         """workers.py:49-123 find_winning_moves_rebuilt on the device for G positions (see
@@ -467,6 +568,10 @@ class SplitSelfPlayEngine:
         self._join(main)
         return self.status
 
+    def set_active(self, mask=None):
+        for i, e in enumerate(self.engines):
+            e.set_active(None if mask is None else np.asarray(mask).reshape(self.G)[i * self.g:(i + 1) * self.g])
+
     def reset_games(self, mask=None):
         for i, e in enumerate(self.engines):
             e.reset_games(None if mask is None else np.asarray(mask)[i * self.g:(i + 1) * self.g])
@@ -495,6 +600,28 @@ class SplitSelfPlayEngine:
     def root_stats(self):
         parts = [e.root_stats() for e in self.engines]
         return tuple(torch.cat([p[k] for p in parts]) for k in range(5))
+
+
+class MatchBuffers:
+    """Device arrays of one arena match, shared by its engines (BatchedSelfPlayEngine.play_refill): the book of
+    openings (boards int8[n,S,S], players int8[n] = side to move, last_moves int32[n], move_counts int32[n]), the
+    two ticket counters, the finished-games counter and the result arrays indexed by game id = 2 * opening +
+    first mover (winner colour, length, and the moves when ``record_moves``)."""
+
+    def __init__(self, boards, players, last_moves, move_counts, record_moves=False, device="cuda"):
+        b = np.ascontiguousarray(boards, dtype=np.int8)
+        n = b.shape[0]
+        self.n_openings, self.A = int(n), int(b[0].size)
+        dev = torch.device(device)
+        self.boards = torch.as_tensor(b.reshape(n, self.A)).to(dev)
+        self.players = torch.as_tensor(np.ascontiguousarray(players, dtype=np.int8).reshape(n)).to(dev)
+        self.last_moves = torch.as_tensor(np.ascontiguousarray(last_moves, dtype=np.int32).reshape(n)).to(dev)
+        self.move_counts = torch.as_tensor(np.ascontiguousarray(move_counts, dtype=np.int32).reshape(n)).to(dev)
+        self.tickets = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.winner = torch.full((2 * n,), 2, dtype=torch.int8, device=dev)  # 2 = not finished
+        self.length = torch.zeros(2 * n, dtype=torch.int32, device=dev)
+        self.moves = torch.full((2 * n, self.A), -1, dtype=torch.int16, device=dev) if record_moves else None
 
 
 def slot_need_table(ecfg, A, mode, lib=None):

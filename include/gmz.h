@@ -191,6 +191,53 @@ int gmz_engine_root_stats(gmz_engine *e, int32_t *visits_dev, int32_t *root_n_de
  * (node header count; with compact child lists the longest list), *out on the host.  Synchronous. */
 int gmz_engine_max_visited_children(gmz_engine *e, int32_t *out);
 
+/* ------------------------------------------------------------------ arena (matches between two networks)
+ * Additive entry points (ABI stays 10).  None of them synchronises the host; each validates its arguments and
+ * capacities before any launch and fails with nothing written. */
+/* Active mask: mask_dev uint8[G] is copied (stream-ordered) into the engine and holds from the next
+ * gmz_engine_begin_move on; NULL = every game active (the engine's state at creation).  An inactive game (byte 0)
+ * gets an empty legal set and n_legal = 0 in gmz_engine_begin_move: it joins no wave (in_slot = out_slot = -1),
+ * adds nothing to the tree counters, gmz_engine_finish_move gives it action -1 and gmz_engine_play leaves it
+ * untouched with status 3.  Active games are searched exactly as without a mask. */
+int gmz_engine_set_active(gmz_engine *e, const uint8_t *mask_dev, void *stream);
+/* Simulations per search from the next gmz_engine_begin_move on: 1 <= num_simulations <= the engine's
+ * gmz_engine_cfg.num_simulations (the node pools were sized for that).  The searches are then exactly those of an
+ * engine created with this budget (an arena gives each network its own).  Call it between moves; the caller's
+ * gmz_engine_waves_for_legal must use the same number.  Host state only: nothing is launched. */
+int gmz_engine_set_simulations(gmz_engine *e, int num_simulations);
+/* gmz_engine_play (no reset) plus the match bookkeeping of an arena, in one launch.  The engine's G slots play the
+ * 2 * n_openings games of a match between network 0 and network 1: game id = 2 * opening + first mover.
+ * Per slot g:
+ *   1. do_move(action_dev[g]) + get_game_ended as gmz_engine_play -> status_dev[g] (action < 0: status 3);
+ *   2. a slot with a game (slot_game_dev[g] >= 0) that played: the move goes to res_moves_dev[id][ply] (int16, row
+ *      stride moves_stride >= A; NULL = not recorded), slot_ply_dev[g] += 1; if the game ended, res_winner_dev[id] =
+ *      the winner's colour (+1 / -1, 0 draw), res_length_dev[id] = moves played since the opening, *finished_dev += 1
+ *      (atomic) and the slot becomes idle (slot_game_dev[g] = -1);
+ *   3. an idle slot draws ticket t = tickets_dev[next_net]++ (atomic; not drawn once the counter has reached
+ *      n_openings): t < n_openings starts game 2 t + next_net, i.e. opening t of the book (book_boards_dev
+ *      int8[n][A], book_players_dev int8[n] side to move, book_last_dev int32[n] last stone or -1, book_counts_dev
+ *      int32[n] stones) is loaded into the slot, slot_game_dev[g] = id, slot_key_dev[g] = t (the key of
+ *      gmz_gumbel_keyed), slot_ply_dev[g] = 0 and the slot is set active; otherwise it is set inactive
+ *      (gmz_engine_set_active's mask; it draws again at the next call).
+ *   4. n_legal_dev[g] = empty cells of the slot's board, 0 for an inactive slot (the host's wave count).
+ * next_net (0 / 1): the network that moves next on this engine; all its active slots have the same network to
+ * move, so a game whose first mover is network i starts only at a call with next_net == i.  Before the first call
+ * slot_game_dev must hold -1 and tickets_dev / finished_dev 0; the first call (every action -1) fills the slots.
+ * tickets_dev int32[2], finished_dev int32[1] and the result arrays may be shared by engines on different streams.
+ * slot_capacity: elements of slot_game_dev / slot_key_dev / slot_ply_dev / n_legal_dev (>= G);
+ * res_capacity: games the result arrays hold (>= 2 * n_openings).  The call switches the engine to its mask. */
+int gmz_engine_play_refill(gmz_engine *e, const int32_t *action_dev, int8_t *status_dev, const int8_t *book_boards_dev,
+                           const int8_t *book_players_dev, const int32_t *book_last_dev, const int32_t *book_counts_dev,
+                           int n_openings, int32_t *tickets_dev, int next_net, int32_t *slot_game_dev,
+                           uint32_t *slot_key_dev, uint32_t *slot_ply_dev, int32_t *n_legal_dev, int slot_capacity,
+                           int8_t *res_winner_dev, int32_t *res_length_dev, int16_t *res_moves_dev, int moves_stride,
+                           int res_capacity, int32_t *finished_dev, void *stream);
+/* Gumbel(0, 1) noise out_dev f64[G][A] from gmz_engine_begin_move's device generator with keys_dev[g] in place of
+ * the game index (g + game_offset) and plies_dev[g] in place of the move counter: row g depends on (seed, key, ply)
+ * alone.  Passed to gmz_engine_begin_move as its explicit gumbel_dev.  out_bytes >= G * A * 8. */
+int gmz_gumbel_keyed(const uint32_t *keys_dev, const uint32_t *plies_dev, uint64_t seed, int G, int A, double *out_dev,
+                     size_t out_bytes, void *stream);
+
 /* ------------------------------------------------------------------ HashNet test network */
 /* Deterministic integer-hash network (definition: oracle/hashnet.py) used for tree parity.
  * Hidden state = uint32 id per slot in hid_pool_dev[G*slots].
