@@ -61,7 +61,8 @@ _SIGS = {
     "gmz_engine_set_active": ([P, P, P], I),
     "gmz_engine_set_simulations": ([P, I], I),
     "gmz_engine_play_refill": ([P, P, P, P, P, P, P, I, P, I, P, P, P, P, I, P, P, P, I, I, P, P], I),
-    "gmz_gumbel_keyed": ([P, P, U64, I, I, P, SZ, P], I),
+    "gmz_replay_ingest": ([I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, P, SZ, P, P, P], I),
+    "gmz_gumbel_keyed":([P, P, U64, I, I, P, SZ, P], I),
     "gmz_hashnet_initial": ([P, I, I, P, P, P, P, P], I),
     "gmz_hashnet_recurrent": ([P, P, P, P, I, I, P, P, P, P], I),
     "gmz_bn_workspace_bytes": ([I, I, I, I, ctypes.POINTER(ctypes.c_size_t)], I),

@@ -11,7 +11,9 @@ own share of the work, time-sliced on its GPU:
               move history kept on the device and harvested one move behind (worker.GameHistory);
   replay      every finished game becomes the reference's TrainingSlices (records.py semantics,
               built as arrays by ``slices_from_game``) appended to THIS rank's device-resident
-              replay shard (trainer.ReplayBuffer) — no data crosses ranks;
+              replay shard (trainer.ReplayBuffer) — no data crosses ranks; ``device_ingest=True``: the
+              slices go from the device history into the shard by one HIP launch per move
+              (gmz_replay_ingest, bit-identical; nothing but a job table crosses the bus);
   training    data-parallel: each rank samples its batch from its own shard; gradients are averaged
               by one flat-bucket all-reduce per step (RCCL over xGMI); PER (sharded):
               IS weights from the global slice count (all-reduce SUM) normalised by the global batch
@@ -79,10 +81,25 @@ class SelfPlay:
         self.missed = (torch.zeros(self.G, dtype=torch.int32, device=dev), torch.zeros(self.G, dtype=torch.int32, device=dev))
         self.pending = None
         self.moves = 0
+        self.ingest_buffer = self.ingest_stream = None
+
+    def ingest_into(self, buffer, stream=None):
+        """Device hand-over: from now on ``step`` / ``flush`` write finished games straight into
+        ``buffer`` (trainer.ReplayBuffer.ingest_history, one HIP launch per move, on ``stream`` or the
+        current one) and return only their (game, winner, n_moves, missed_fives, missed_totals)."""
+        self.ingest_buffer, self.ingest_stream = buffer, stream
+
+    def _finished(self, sn):
+        if self.ingest_buffer is None:
+            return self.hist.harvest(sn)
+        if self.ingest_stream is None:
+            return self.ingest_buffer.ingest_history(self.hist, sn)
+        with torch.cuda.stream(self.ingest_stream):
+            return self.ingest_buffer.ingest_history(self.hist, sn)
 
     def step(self):
         """Play one move of every game; returns the games that finished one move earlier
-        (GameHistory.harvest tuples)."""
+        (GameHistory.harvest tuples; after ``ingest_into`` their first five fields)."""
         e, h = self.eng, self.hist
         b, p, lm, mc = e.game_state()
         pol, val, act = e.search()
@@ -90,13 +107,13 @@ class SelfPlay:
         h.record(b, p, lm, mc, pol, val, act)
         status = e.play(reset_finished=True)
         sn = h.after_play(status, mc, act, *self.missed)
-        done = h.harvest(self.pending)
+        done = self._finished(self.pending)
         self.pending = sn
         self.moves += 1
         return done
 
     def flush(self):
-        done = self.hist.harvest(self.pending)
+        done = self._finished(self.pending)
         self.pending = None
         return done
 
@@ -111,7 +128,8 @@ class C4Loop:
     """The composed loop on one rank (see module docstring).  ``dist``: torch.distributed or None."""
 
     def __init__(self, selfplay, trainer, buffer, cfg, batch_size, dist=None, moves_per_iter=1,
-                 train_steps_per_iter=1, model_update_interval=1000, seed=0, device="cuda", concurrent=False):
+                 train_steps_per_iter=1, model_update_interval=1000, seed=0, device="cuda", concurrent=False,
+                 device_ingest=False):
         self.sp, self.tr, self.rb, self.cfg = selfplay, trainer, buffer, cfg
         self.B, self.dist = int(batch_size), dist
         self.moves_per_iter, self.train_steps_per_iter = int(moves_per_iter), int(train_steps_per_iter)
@@ -130,14 +148,27 @@ class C4Loop:
         # the self-play engines fork every move from this stream: weight swaps are enqueued on it
         self.sp_stream = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
         self._train_done = None
+        # device_ingest: finished games go from the self-play history to the shard in HIP (one launch per
+        # move, GameHistory.ingest) on the stream of every other ring operation; off = the host path
+        self.device_ingest = bool(device_ingest)
+        if self.device_ingest:
+            if not hasattr(getattr(selfplay, "hist", None), "ingest") or not hasattr(selfplay, "ingest_into"):
+                raise ValueError("device_ingest needs a self-play source with a device history (loop.SelfPlay)")
+            if self.device.type != "cuda":
+                raise ValueError("device_ingest needs the loop on a GPU")
+            if (cfg.BOARD_SIZE, cfg.NUM_UNROLL_STEPS, cfg.N_STEPS, cfg.DISCOUNT) != tuple(
+                    getattr(buffer.cfg, k) for k in ("BOARD_SIZE", "NUM_UNROLL_STEPS", "N_STEPS", "DISCOUNT")):
+                raise ValueError("device_ingest: the loop's config and the buffer's disagree on the slices' geometry")
+            selfplay.ingest_into(buffer, self.train_stream)
 
     # ---------------------------------------------------------------- pieces
     def _add_games(self, done):
         c = self.cfg
-        for (g, winner, n, mf, mt, boards, players, lasts, pols, vals, acts) in done:
-            arrs = slices_from_game(boards, players, lasts, pols, vals, acts, winner, c.BOARD_SIZE, c.DISCOUNT,
-                                    c.N_STEPS, c.NUM_UNROLL_STEPS)
-            self.rb.add_arrays(*arrs)
+        for item in done:
+            g, winner, n, mf, mt = item[:5]
+            if not self.device_ingest:  # device_ingest: SelfPlay.step has written the slices already
+                arrs = slices_from_game(*item[5:], winner, c.BOARD_SIZE, c.DISCOUNT, c.N_STEPS, c.NUM_UNROLL_STEPS)
+                self.rb.add_arrays(*arrs)
             self.games += 1
             self.slices += n
             self.game_lengths.append(n)
@@ -250,7 +281,8 @@ def run_c4(args, rank, world, dist, backend, log=print):
     loop = C4Loop(sp, tr, rb, tcfg, args.trainer_batch, dist=dist if world > 1 else None,
                   moves_per_iter=args.loop_moves_per_iter, train_steps_per_iter=args.loop_train_per_iter,
                   model_update_interval=args.loop_update_interval, seed=args.seed,
-                  concurrent=getattr(args, "loop_concurrent", False))
+                  concurrent=getattr(args, "loop_concurrent", False),
+                  device_ingest=getattr(args, "loop_device_ingest", False))
     t_w = time.perf_counter()
     loop.run(args.loop_warmup)
     torch.cuda.synchronize()

@@ -2174,6 +2174,34 @@ class ReplayBuffer:
         self.ptr = (self.ptr + n) % self.N
         self.count = min(self.N, self.count + n)
 
+    def admission_priority(self):
+        """The priority of newly added slices as a device f32 scalar, or None for 1.0 (PER off, or no
+        priority updated yet): what gmz_replay_ingest reads on the device, so nothing synchronises."""
+        m = self.max_priority
+        if not self.cfg.ENABLE_PER or (not torch.is_tensor(m) and float(m) == 1.0):
+            return None
+        if not (torch.is_tensor(m) and m.dtype == torch.float32 and m.device == self.obs.device):
+            m = self.max_priority = torch.as_tensor(m, dtype=torch.float32).to(self.obs.device)
+        return m
+
+    def ingest_history(self, hist, sn, games=None):
+        """The finished games of ``hist``'s snapshot ``sn`` (worker.GameHistory) appended on the device: their
+        slices go from the history's banks into this ring by one HIP launch (gmz_replay_ingest) on the
+        current stream, bit-identical to GameHistory.harvest + loop.slices_from_game + :meth:`add_arrays`
+        game by game.  Returns the per-game (game slot, winner, n_moves, missed_fives, missed_totals)."""
+        c = self.cfg
+        U, H = int(c.NUM_UNROLL_STEPS), int(c.BOARD_SIZE)
+        if self.obs.device.type != "cuda":
+            raise ValueError("ingest_history needs a device-resident ReplayBuffer, not one on %s" % self.obs.device)
+        if getattr(hist, "A", None) != H * H or tuple(self.obs.shape[1:]) != (U + 1, 3, H, H):
+            raise ValueError("history of %s actions does not fit a ring of %dx%d boards, %d unroll steps"
+                             % (getattr(hist, "A", None), H, H, U))
+        if U < 1 or self.N < 1:
+            raise ValueError("ring of %d slices, %d unroll steps: smaller than one slice" % (self.N, U))
+        if hist.board.device != self.obs.device:
+            raise ValueError("history on %s, ring on %s" % (hist.board.device, self.obs.device))
+        return hist.ingest(sn, self, games=games)
+
     def sample(self, B, rng=np.random, dist=None):
         """replay_buffer.py:58-94.  ``dist``: torch.distributed when this buffer is one rank's shard of
         a data-parallel trainer (sharded PER): each rank samples its B slices from its

@@ -53,6 +53,34 @@ def board_states_to_obs(boards, players, last_moves, H):
     return obs
 
 
+def replay_jobs(games, ptr, count, N):
+    """Job table of gmz_replay_ingest for ``games`` = [(slot, bank, row0, n_moves, winner), ...] appended in
+    this order to a ring of N slices at ``ptr`` holding ``count``: what ReplayBuffer.add_arrays does game by
+    game (a game longer than the ring keeps its newest N slices, written from ``ptr`` on), with every
+    slice that a later game of the same table would overwrite left out, so no two kept slices share a
+    ring slot.  Such slices are always the oldest of their game: a drop from the front.
+    Returns (jobs int32 [J, 8] = game, bank, row0, n, winner, drop, slot, first; new ptr; new count)."""
+    N, p = int(N), int(ptr)
+    starts = []
+    for (_, _, _, n, _) in games:
+        k = min(int(n), N)
+        starts.append(p)
+        p = (p + k) % N
+        count = min(N, int(count) + k)
+    rows, cover = [], 0  # cover: ring slots written by the games after this one, a run from this game's end on
+    for (g, bk, s0, n, w), st in zip(reversed(games), reversed(starts)):
+        k = min(int(n), N)
+        over = min(k, max(0, cover - (N - k)))
+        if k > over:
+            rows.append((g, bk, s0, n, w, n - k + over, (st + over) % N, 0))
+        cover = min(N, cover + k)
+    jobs = np.asarray(rows[::-1], dtype=np.int32).reshape(-1, 8)
+    if len(jobs):
+        kept = jobs[:, 3] - jobs[:, 5]
+        jobs[:, 7] = np.cumsum(kept) - kept
+    return jobs, p, count
+
+
 class GameHistory:
     """Per-game move history kept on the device, harvested one move behind (no per-move host sync).
 
@@ -63,7 +91,11 @@ class GameHistory:
     game that just ended, so the next game of that slot writes the other bank.  ``harvest`` (called
     after the NEXT move has been queued) waits for that event — already passed by then — and copies
     each finished game's rows to the host with DMA copies on a side stream.  A bank is rewritten only
-    when its slot's next game ends too, at least 2*N_IN_ROW-1 moves later, long after the harvest."""
+    when its slot's next game ends too, at least 2*N_IN_ROW-1 moves later, long after the harvest.
+    ``ingest`` is the harvest that never leaves the device: the finished games' TrainingSlices go from
+    the banks into a trainer.ReplayBuffer by one gmz_replay_ingest launch; only the job table (32 bytes
+    per game) crosses the bus.  ``record`` makes its stream wait for the last ingest launch, so a bank
+    is never rewritten before an ingest on another stream has read it."""
 
     def __init__(self, G, A, device, min_game_len=9):
         assert min_game_len >= 2, "a bank must survive one move after its game ended"
@@ -86,6 +118,9 @@ class GameHistory:
         pin = lambda dt: torch.zeros(G, dtype=dt).pin_memory()  # noqa: E731
         self.snaps = [dict(status=pin(torch.int8), mc=pin(torch.int32), bank=pin(torch.int64), mf=pin(torch.int32),
                            mt=pin(torch.int32), act=pin(torch.int32), ev=None) for _ in range(2)]
+        self._tables = None     # ingest: pinned + device job tables, rotating behind events
+        self._tk = 0
+        self._ingest_ev = None  # the last ingest launch; the next record() waits for it on its stream
 
     def set_start(self, move_counts):
         """The current games start from positions with ``move_counts`` stones (before their first
@@ -96,7 +131,10 @@ class GameHistory:
 
     def record(self, boards, players, last_moves, move_counts, policy, value, action):
         """Append this move's search inputs/outputs (all device tensors, before the move is played)."""
-        i = (self.bank, self.gidx, move_counts.long().clamp(0, self.L - 1))
+        if self._ingest_ev is not None:  # device-side wait: the banks an ingest on another stream still reads
+            torch.cuda.current_stream(self.dev).wait_event(self._ingest_ev)
+            self._ingest_ev = None
+        i =(self.bank, self.gidx, move_counts.long().clamp(0, self.L - 1))
         self.board[i] = boards.reshape(self.G, self.A)
         self.player[i] = players
         self.last[i] = last_moves
@@ -121,11 +159,35 @@ class GameHistory:
         self.bank ^= ended.long()
         return sn
 
-    def harvest(self, sn):
+    def harvest(self, sn, games=None):
         """Finished games of snapshot ``sn`` -> list of (game index, winner, n_moves, missed_fives,
         missed_totals, boards int8[n,A], players int8[n], last_moves int32[n], policies f64[n,A],
         values f32[n], actions int32[n]) on the host.  Games whose search found no legal move
-        (action -1, workers.py:169-170) are abandoned without a record, as the reference does."""
+        (action -1, workers.py:169-170) are abandoned without a record, as the reference does.
+        ``games``: ``finished(sn)`` when the caller has taken it already."""
+        fin = self.finished(sn) if games is None else games
+        out = []
+        if len(fin) == 0:
+            return out
+        jobs = []
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(sn["ev"])
+            for (g, bk, s0, n, winner, mf, mt) in fin:
+                host = [torch.empty((n,) + tuple(t.shape[3:]), dtype=t.dtype, pin_memory=True)
+                        for t in (self.board, self.player, self.last, self.pol, self.val, self.act)]
+                for h, t in zip(host, (self.board, self.player, self.last, self.pol, self.val, self.act)):
+                    h.copy_(t[bk, g, s0:s0 + n], non_blocking=True)
+                jobs.append((g, winner, n, mf, mt, host))
+        self.side.synchronize()
+        for g, winner, n, mf, mt, host in jobs:
+            out.append((g, winner, n, mf, mt) + tuple(h.numpy() for h in host))
+        return out
+
+    def finished(self, sn):
+        """The games that ended at snapshot ``sn`` (waits for its event), in slot order: list of (game slot,
+        bank, first recorded row, n_moves, winner, missed_fives, missed_totals).  Abandoned games (action
+        -1) are left out.  Every ended slot's bank restarts from row 0, so a snapshot is read once: by
+        ``harvest``, by ``ingest``, or by a caller that hands this list to both."""
         if sn is None or sn["ev"] is None:
             return []
         sn["ev"].synchronize()
@@ -134,26 +196,66 @@ class GameHistory:
         out = []
         if len(fin) == 0:
             return out
-        mc, bank, act = sn["mc"].numpy(), sn["bank"].numpy(), sn["act"].numpy()
-        jobs = []
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(sn["ev"])
-            for g in fin:
-                bk = int(bank[g])
-                s0 = int(self.start[bk, g])
-                self.start[bk, g] = 0  # this bank's next game starts from the empty board
-                if act[g] < 0:
-                    continue
-                n = int(mc[g]) + 1 - s0
-                host = [torch.empty((n,) + tuple(t.shape[3:]), dtype=t.dtype, pin_memory=True)
-                        for t in (self.board, self.player, self.last, self.pol, self.val, self.act)]
-                for h, t in zip(host, (self.board, self.player, self.last, self.pol, self.val, self.act)):
-                    h.copy_(t[bk, g, s0:s0 + n], non_blocking=True)
-                jobs.append((int(g), int(st[g]), n, int(sn["mf"][g]), int(sn["mt"][g]), host))
-        self.side.synchronize()
-        for g, winner, n, mf, mt, host in jobs:
-            out.append((g, winner, n, mf, mt) + tuple(h.numpy() for h in host))
+        mc, bank, act, mf, mt = (sn[k].numpy() for k in ("mc", "bank", "act", "mf", "mt"))
+        for g in fin:
+            bk = int(bank[g])
+            s0 = int(self.start[bk, g])
+            self.start[bk, g] = 0  # this bank's next game starts from the empty board
+            if act[g] < 0:
+                continue
+            out.append((int(g), bk, s0, int(mc[g]) + 1 - s0, int(st[g]), int(mf[g]), int(mt[g])))
         return out
+
+    def _job_tables(self):
+        """The next (pinned table, device table, event) of the rotation; waits until the launch that last read
+        this pair has passed (two launches back: long passed)."""
+        if self._tables is None:
+            self._tables = [[torch.zeros(self.G, 8, dtype=torch.int32).pin_memory(),
+                             torch.zeros(self.G, 8, dtype=torch.int32, device=self.dev), None] for _ in range(2)]
+        t = self._tables[self._tk & 1]
+        self._tk += 1
+        if t[2] is not None:
+            t[2].synchronize()
+        return t
+
+    def ingest(self, sn, rb, games=None):
+        """``harvest`` without the host: the TrainingSlices of the games that ended at snapshot ``sn`` are
+        written from the banks into ``rb`` (a device trainer.ReplayBuffer of this board size) by one
+        gmz_replay_ingest launch on the current stream, bit-identical to harvest + loop.slices_from_game
+        + ReplayBuffer.add_arrays game by game in slot order (discount, n-step and unroll from rb.cfg).
+        ``games``: ``finished(sn)`` when the caller has taken it already.  Returns the per-game
+        (game slot, winner, n_moves, missed_fives, missed_totals)."""
+        from ._lib import check, load, nbytes, ptr, stream_ptr
+        import ctypes
+        if games is None:
+            games = self.finished(sn)
+        if not games:
+            return []
+        c = rb.cfg
+        jobs, new_ptr, new_count = replay_jobs([x[:5] for x in games], rb.ptr, rb.count, rb.N)
+        J = len(jobs)
+        if J > self.G:
+            raise ValueError("%d finished games in one snapshot of %d slots" % (J, self.G))
+        if J:
+            stream = torch.cuda.current_stream(self.dev)
+            stream.wait_event(sn["ev"])  # the banks' rows were written before the snapshot
+            tab = self._job_tables()
+            pinned, dev = tab[0], tab[1]
+            pinned[:J] = torch.from_numpy(jobs)
+            dev[:J].copy_(pinned[:J], non_blocking=True)
+            n_steps = int(c.N_STEPS)
+            pw = (ctypes.c_double * (n_steps + 1))(*[c.DISCOUNT ** i for i in range(n_steps + 1)])
+            prio = rb.admission_priority()
+            check(load().gmz_replay_ingest(
+                int(c.BOARD_SIZE), int(c.NUM_UNROLL_STEPS), n_steps, self.G, self.L, ptr(self.board), ptr(self.player),
+                ptr(self.last), ptr(self.pol), ptr(self.val), ptr(self.act), ptr(rb.obs), ptr(rb.act), ptr(rb.rew),
+                ptr(rb.pol), ptr(rb.val), ptr(rb.prio), rb.N, ptr(pinned), J, ptr(dev), nbytes(dev), pw, ptr(prio),
+                stream_ptr(stream)))
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            tab[2] = self._ingest_ev = ev
+        rb.ptr, rb.count = new_ptr, new_count
+        return [(g, w, n, mf, mt) for (g, _, _, n, w, mf, mt) in games]
 
 
 def gpu_selfplay_worker(worker_id, worker_mode, data_queue, log_status_queue, ui_queue, shutdown_event,

@@ -608,6 +608,35 @@ int gmz_head_conv1x1_backward(int dtype, const void *x_dev, long P, int C, const
                               const void *dy0_dev, const void *dy1_dev, void *dx_dev, float *dw0_dev, float *db0_dev,
                               float *dw1_dev, float *db1_dev, int accumulate, void *ws_dev, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ replay ingest (worker.GameHistory -> ring) */
+/* Finished self-play games go from the device move history straight into the trainer's device replay ring: one
+ * launch writes every kept TrainingSlice of every job, bit-identical to records.final_rewards +
+ * records.compute_n_step_returns + loop.slices_from_game + ReplayBuffer.add_arrays on the host.
+ * History (bank b, game g, row r): board int8 [2][G][L][A], player int8 [2][G][L], last int32 [2][G][L] (-1 = none),
+ * policy f64 [2][G][L][A], value f32 [2][G][L], action int32 [2][G][L]; A = board_size^2, board_size 5..22.
+ * Ring of N slices: obs u8 [N][U+1][3][A], act int32 [N][U], rew f32 [N][U], pol f32 [N][U+1][A], val f32 [N][U+1],
+ * prio f32 [N].
+ * Job record (32 bytes, 8 int32): game, bank, row0 (first recorded row), n (recorded
+ * moves), winner (+1 / -1, 0 draw), drop (slices left out from the front), slot (ring slot of the first kept
+ * slice; kept slice k goes to (slot + k) mod N), first (kept slices of the jobs before it).  Slice t of a game covers
+ * moves t .. t+U; rewards, value targets, planes, policies and actions as the host path computes them, zero (action
+ * -1) past the game.
+ * The table is given twice: jobs_host is validated before anything is launched; the kernel reads jobs_dev
+ * (jobs_dev_bytes >= n_jobs records; the caller's copy of the same table, ordered before this call on `stream`).
+ * Refused, nothing launched: board_size outside 5..22, unroll < 1, n_steps outside 1..GMZ_REPLAY_MAX_N_STEPS, a short
+ * device table, game >= G, bank outside {0, 1}, rows that pass L, drop outside 0..n-1, slot >= N, a wrong `first`,
+ * kept slices that exceed N in total or overlap in the ring.  n_jobs == 0 launches nothing and succeeds.
+ * discount_pow: host f64 [n_steps + 1], discount**i as the caller's arithmetic gives it (passed to the kernel by
+ * value; the device computes no power).  priority_dev: device f32 [1], the admission priority written to prio of
+ * every kept slice, read by the kernel; NULL = 1.0. */
+#define GMZ_REPLAY_MAX_N_STEPS 32
+int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G, int L, const int8_t *hist_board_dev,
+                      const int8_t *hist_player_dev, const int32_t *hist_last_dev, const double *hist_policy_dev,
+                      const float *hist_value_dev, const int32_t *hist_action_dev, uint8_t *ring_obs_dev,
+                      int32_t *ring_act_dev, float *ring_rew_dev, float *ring_pol_dev, float *ring_val_dev,
+                      float *ring_prio_dev, int N, const void *jobs_host, int n_jobs, const void *jobs_dev,
+                      size_t jobs_dev_bytes, const double *discount_pow, const float *priority_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
