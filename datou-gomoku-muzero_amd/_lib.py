@@ -171,3 +171,22 @@ def nbytes(t):
 def stream_ptr(stream=None):
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)
+
+
+def call(name, *args):
+    """check(lib.<name>(*args)); a torch.Tensor argument is passed as its data pointer, None as NULL."""
+    return check(getattr(load(), name)(*[ptr(a) if isinstance(a, torch.Tensor) else a for a in args]))
+
+
+_QUERIED = {}
+
+
+def query(name, *args, ctype=ctypes.c_size_t):
+    """The value a gmz_*_bytes / gmz_*_slots entry point writes through its last (out) argument; cached per
+    (name, args)."""
+    key = (name, args)
+    if key not in _QUERIED:
+        out = ctype()
+        call(name, *args, ctypes.byref(out))
+        _QUERIED[key] = out.value
+    return _QUERIED[key]

@@ -25,6 +25,7 @@ training-mode BatchNorm run on the HIP kernels of csrc/gmz_conv.hip / csrc/gmz_t
 trunks' first convolutions, 1x1 convolutions and Linears run on MIOpen / hipBLASLt.
 """
 import collections
+import contextlib
 import math
 from dataclasses import dataclass, field, asdict
 
@@ -227,14 +228,9 @@ class _PendingBN:
 
 def _conv_takes_pending(conv, z):
     """True when ``_conv3_apply(conv, y)`` of a training-mode BatchNorm output y of z's shape, dtype and layout
-    runs the HIP conv that can apply the BatchNorm in its prologue (the conditions of its single-segment path)."""
-    if not (DEFER_BN_APPLY and FUSED_BN and FUSED_CONV and not RELU_MASK and not FUSED_BN_BWD_STATS and z.is_cuda
-            and z.dim() == 4 and z.shape[1] == 128 and z.shape[2] == z.shape[3] and z.shape[2] in HIP_CONV_SIZES):
-        return False
-    if conv.weight.shape != (128, 128, 3, 3) or conv.bias is not None:
-        return False
-    dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else z.dtype
-    return dt == z.dtype and dt in _CONV_DTYPES and z.is_contiguous(memory_format=torch.channels_last)
+    runs the HIP conv that can apply the BatchNorm in its prologue (``_hip_conv_dtype``, in y's own dtype)."""
+    return bool(DEFER_BN_APPLY and FUSED_BN and not RELU_MASK and not FUSED_BN_BWD_STATS
+                and _hip_conv_dtype(conv, z) == z.dtype)
 
 
 class _FusedMaskedBN(torch.autograd.Function):
@@ -248,7 +244,6 @@ class _FusedMaskedBN(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, res, mask, running_mean, running_var, num_batches, eps, momentum, relu,
                 stats=None, link=None, bwd_link=False, defer=False):
         from . import _lib
-        L = _lib.load()
         layout = _bn_layout(x)
         if layout is None:
             x, layout = x.contiguous(), 0
@@ -262,46 +257,25 @@ class _FusedMaskedBN(torch.autograd.Function):
         if (RELU_MASK and relu and layout == 1 and C % 8 == 0 and x.dtype != torch.float32 and torch.is_grad_enabled()
                 and _aligned16(x, res, y) and not (FUSED_BN_BWD_STATS and bwd_link)):
             rmask = torch.empty(B * S * (C // 8), dtype=torch.uint8, device=x.device)
+        # the argument runs the five entry points share: the update of the running statistics, the affine pass and
+        # its outputs, the producing conv's statistics partials, and the tail (the _m variants take the ReLU mask)
+        dt, stream = _BN_DTYPES[x.dtype], _lib.stream_ptr()
+        running = (float(eps), float(momentum), running_mean, running_var, num_batches)
+        affine = (gamma, beta, *running, int(relu), y, save)
+        partials = (None, 0, 0) if stats is None else (stats[0], int(stats[1]), _lib.nbytes(stats[0]))
+        m, tail = ("", (stream,)) if rmask is None else ("_m", (rmask, stream))
         if defer and layout == 1 and rmask is None and _aligned16(x, res, y):
             # DEFER_BN_APPLY: statistics and running stats now; y is written by the consuming conv's prologue
             # (gmz_conv3x3_forward_bnapply, _conv3_apply), which the caller guarantees comes next
             ws = None if stats is not None else _bn_workspace(1, B, C, S, x.device)
-            _lib.check(L.gmz_bn_forward_deferred(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(mask), B, C, S, float(eps),
-                                                 float(momentum), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                                 _lib.ptr(num_batches), _lib.ptr(save),
-                                                 None if stats is None else _lib.ptr(stats[0]),
-                                                 0 if stats is None else int(stats[1]),
-                                                 0 if stats is None else _lib.nbytes(stats[0]), _lib.ptr(ws),
-                                                 _lib.nbytes(ws), _lib.stream_ptr()))
+            _lib.call("gmz_bn_forward_deferred", dt, x, mask, B, C, S, *running, save, *partials, ws, _lib.nbytes(ws),
+                      stream)
             y._gmz_pending = _PendingBN(x, res, gamma, beta, save, relu)
         elif stats is not None and layout == 1:  # statistics reduced by the producing conv's epilogue
-            if rmask is not None:
-                _lib.check(L.gmz_bn_forward_stats_m(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(res), B, C, S,
-                                                    _lib.ptr(gamma), _lib.ptr(beta), float(eps), float(momentum),
-                                                    _lib.ptr(running_mean), _lib.ptr(running_var),
-                                                    _lib.ptr(num_batches), int(relu), _lib.ptr(y), _lib.ptr(save),
-                                                    _lib.ptr(stats[0]), int(stats[1]), _lib.nbytes(stats[0]),
-                                                    _lib.ptr(rmask), _lib.stream_ptr()))
-            else:
-                _lib.check(L.gmz_bn_forward_stats(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(res), B, C, S,
-                                                  _lib.ptr(gamma), _lib.ptr(beta), float(eps), float(momentum),
-                                                  _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(num_batches),
-                                                  int(relu), _lib.ptr(y), _lib.ptr(save), _lib.ptr(stats[0]),
-                                                  int(stats[1]), _lib.nbytes(stats[0]), _lib.stream_ptr()))
+            _lib.call("gmz_bn_forward_stats" + m, dt, x, res, B, C, S, *affine, *partials, *tail)
         else:
             ws = _bn_workspace(layout, B, C, S, x.device)
-            if rmask is not None:
-                _lib.check(L.gmz_bn_forward_m(_BN_DTYPES[x.dtype], layout, _lib.ptr(x), _lib.ptr(res), _lib.ptr(mask),
-                                              B, C, S, _lib.ptr(gamma), _lib.ptr(beta), float(eps), float(momentum),
-                                              _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(num_batches),
-                                              int(relu), _lib.ptr(y), _lib.ptr(save), _lib.ptr(ws), _lib.nbytes(ws),
-                                              _lib.ptr(rmask), _lib.stream_ptr()))
-            else:
-                _lib.check(L.gmz_bn_forward(_BN_DTYPES[x.dtype], layout, _lib.ptr(x), _lib.ptr(res), _lib.ptr(mask), B,
-                                            C, S, _lib.ptr(gamma), _lib.ptr(beta), float(eps), float(momentum),
-                                            _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(num_batches),
-                                            int(relu), _lib.ptr(y), _lib.ptr(save), _lib.ptr(ws), _lib.nbytes(ws),
-                                            _lib.stream_ptr()))
+            _lib.call("gmz_bn_forward" + m, dt, layout, x, res, mask, B, C, S, *affine, ws, _lib.nbytes(ws), *tail)
         ctx.save_for_backward(x, y, mask, gamma, save)
         ctx.relu, ctx.has_res, ctx.layout = relu, res is not None, layout
         ctx.rmask = rmask
@@ -316,7 +290,6 @@ class _FusedMaskedBN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         from . import _lib
-        L = _lib.load()
         x, y, mask, gamma, save = ctx.saved_tensors
         layout = ctx.layout
         dy = _like(dy, layout)
@@ -339,25 +312,18 @@ class _FusedMaskedBN(torch.autograd.Function):
         pre = bl.bwd if bl is not None else None
         if bl is not None:
             bl.bwd = None
+        # what the three entry points share: the saved forward, the incoming gradient and the four outputs
+        dt, stream = _BN_DTYPES[x.dtype], _lib.stream_ptr()
+        grads = (x, y, dy, mask, B, C, S, gamma, save, int(ctx.relu), dx, dres, dgamma, dbeta)
         if pre is not None and (pre[2] is dy or (pre[2].data_ptr() == dy.data_ptr() and pre[2].stride() == dy.stride()
                                                  and pre[2].dtype == dy.dtype)):
             # dz sums already reduced by the conv that produced dy (gmz_conv3x3_forward_bwdstats)
-            _lib.check(L.gmz_bn_backward_stats(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(y), _lib.ptr(dy),
-                                               _lib.ptr(mask), B, C, S, _lib.ptr(gamma), _lib.ptr(save), int(ctx.relu),
-                                               _lib.ptr(dx), _lib.ptr(dres), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                               _lib.ptr(pre[0]), int(pre[1]), _lib.nbytes(pre[0]), _lib.ptr(ws),
-                                               _lib.nbytes(ws), _lib.stream_ptr(), int(acc)))
+            _lib.call("gmz_bn_backward_stats", dt, *grads, pre[0], int(pre[1]), _lib.nbytes(pre[0]), ws,
+                      _lib.nbytes(ws), stream, int(acc))
         elif ctx.rmask is not None and _aligned16(x, y, dy, dx, dres):
-            _lib.check(L.gmz_bn_backward_acc_m(_BN_DTYPES[x.dtype], layout, _lib.ptr(x), _lib.ptr(y), _lib.ptr(dy),
-                                               _lib.ptr(mask), B, C, S, _lib.ptr(gamma), _lib.ptr(save), int(ctx.relu),
-                                               _lib.ptr(dx), _lib.ptr(dres), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                               _lib.ptr(ws), _lib.nbytes(ws), _lib.ptr(ctx.rmask), _lib.stream_ptr(),
-                                               int(acc)))
+            _lib.call("gmz_bn_backward_acc_m", dt, layout, *grads, ws, _lib.nbytes(ws), ctx.rmask, stream, int(acc))
         else:
-            _lib.check(L.gmz_bn_backward_acc(_BN_DTYPES[x.dtype], layout, _lib.ptr(x), _lib.ptr(y), _lib.ptr(dy),
-                                             _lib.ptr(mask), B, C, S, _lib.ptr(gamma), _lib.ptr(save), int(ctx.relu),
-                                             _lib.ptr(dx), _lib.ptr(dres), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                             _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr(), int(acc)))
+            _lib.call("gmz_bn_backward_acc", dt, layout, *grads, ws, _lib.nbytes(ws), stream, int(acc))
         ctx.rmask = None
         if ctx.link is not None and dres is not None:
             # the residual's gradient goes to the block's first conv, whose input-gradient epilogue adds it
@@ -368,18 +334,10 @@ class _FusedMaskedBN(torch.autograd.Function):
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None
 
 
-_WS_BYTES = {}
-
-
 def _bn_workspace(layout, B, C, S, device):
-    import ctypes
     from . import _lib
-    key = (layout, B, C, S)
-    if key not in _WS_BYTES:
-        n = ctypes.c_size_t()
-        _lib.check(_lib.load().gmz_bn_workspace_bytes(layout, B, C, S, ctypes.byref(n)))
-        _WS_BYTES[key] = n.value
-    return torch.empty((_WS_BYTES[key] + 7) // 8, dtype=torch.float64, device=device)
+    n = _lib.query("gmz_bn_workspace_bytes", layout, B, C, S)
+    return torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
 
 
 def _bn_act(mod, x, mask=None, res=None, relu=True, link=None, segments=1, consumer=None):
@@ -430,12 +388,9 @@ def _bn_seg(mod, x, mask, res, relu, nseg):
     st = getattr(x, "_gmz_bnstats", None)
     board = st[0] if (st is not None and st[1] == "board") else None
     m = None if mask is None else mask.contiguous().view(torch.uint8)
-    _lib.check(_lib.load().gmz_bn_forward_seg(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(res), _lib.ptr(m), B, nseg, C,
-                                              S, _lib.ptr(mod.weight), _lib.ptr(mod.bias), float(mod.eps),
-                                              float(mod.momentum), _lib.ptr(mod.running_mean), _lib.ptr(mod.running_var),
-                                              _lib.ptr(mod.num_batches_tracked), int(relu), _lib.ptr(y), _lib.ptr(save),
-                                              _lib.ptr(ws), _lib.nbytes(ws), _lib.ptr(board), _lib.nbytes(board),
-                                              _lib.stream_ptr()))
+    _lib.call("gmz_bn_forward_seg", _BN_DTYPES[x.dtype], x, res, m, B, nseg, C, S, mod.weight, mod.bias, float(mod.eps),
+              float(mod.momentum), mod.running_mean, mod.running_var, mod.num_batches_tracked, int(relu), y, save, ws,
+              _lib.nbytes(ws), board, _lib.nbytes(board), _lib.stream_ptr())
     return y
 
 
@@ -450,10 +405,8 @@ def _bn_eval(mod, x, res, relu):
     S = x[0, 0].numel()
     y = torch.empty_like(x)
     ws = _bn_workspace(layout, B, C, S, x.device)
-    _lib.check(_lib.load().gmz_bn_eval(_BN_DTYPES[x.dtype], layout, _lib.ptr(x), _lib.ptr(res), B, C, S,
-                                       _lib.ptr(mod.weight), _lib.ptr(mod.bias), _lib.ptr(mod.running_mean),
-                                       _lib.ptr(mod.running_var), float(mod.eps), int(relu), _lib.ptr(y),
-                                       _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr()))
+    _lib.call("gmz_bn_eval", _BN_DTYPES[x.dtype], layout, x, res, B, C, S, mod.weight, mod.bias, mod.running_mean,
+              mod.running_var, float(mod.eps), int(relu), y, ws, _lib.nbytes(ws), _lib.stream_ptr())
     return y
 
 
@@ -545,8 +498,7 @@ def _packed_conv_weight(w, dtype, transpose, parent=None):
         return hit[1]
     out = hit[1] if hit is not None else torch.empty(147456, dtype=torch.int16, device=w.device)
     s = w.stride()
-    _lib.check(_lib.load().gmz_conv3x3_pack(_CONV_DTYPES[dtype], _lib.ptr(w.detach()), s[0], s[1], s[2], s[3],
-                                            int(transpose), _lib.ptr(out), _lib.stream_ptr()))
+    _lib.call("gmz_conv3x3_pack", _CONV_DTYPES[dtype], w.detach(), *s, int(transpose), out, _lib.stream_ptr())
     # (version, packed, source view, transpose, dtype): _repack_stale re-packs the entry in place from the source
     cache[key] = (owner._version, out, w.detach(), int(transpose), dtype)
     return out
@@ -573,8 +525,7 @@ def _packed_split_weight(w):
         return hit[1]
     out = hit[1] if hit is not None else torch.empty(294912, dtype=torch.int16, device=w.device)
     s = w.stride()
-    _lib.check(_lib.load().gmz_conv3x3_pack_split(_lib.ptr(w.detach()), s[0], s[1], s[2], s[3], 0, _lib.ptr(out),
-                                                  _lib.stream_ptr()))
+    _lib.call("gmz_conv3x3_pack_split", w.detach(), *s, 0, out, _lib.stream_ptr())
     w.__dict__["_gmz_pack_split"] = (w._version, out, w.detach())  # (version, packed, source view)
     return out
 
@@ -591,9 +542,8 @@ def _conv3x3_split_hip(x, packed, bn=None, res=None, relu=False):
         eps = 0.0
     else:
         g, b, m, v, eps = bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps)
-    _lib.check(_lib.load().gmz_conv3x3_forward_split(x.shape[2], _lib.ptr(x), _lib.ptr(packed), _lib.ptr(y), x.shape[0],
-                                                     _lib.ptr(g), _lib.ptr(b), _lib.ptr(m), _lib.ptr(v), eps,
-                                                     _lib.ptr(res), int(bool(relu)), _lib.stream_ptr()))
+    _lib.call("gmz_conv3x3_forward_split", x.shape[2], x, packed, y, x.shape[0], g, b, m, v, eps, res, int(bool(relu)),
+              _lib.stream_ptr())
     return y
 
 
@@ -630,7 +580,7 @@ def _repack_stale(owners, tables, prepare=False):
                 arr[i] = (h[2].data_ptr(), h[2].stride(), h[1].data_ptr(), 0, 0)
             table = tables[sig] = torch.from_numpy(arr.view(np.uint8)).to(split[0][1][1].device)
         if table is not None and not prepare:
-            _lib.check(_lib.load().gmz_conv3x3_pack_split_many(_lib.ptr(table), len(split), _lib.stream_ptr()))
+            _lib.call("gmz_conv3x3_pack_split_many", table, len(split), _lib.stream_ptr())
             for o, h in split:
                 o.__dict__["_gmz_pack_split"] = (o._version,) + tuple(h[1:])
             n += len(split)
@@ -640,13 +590,9 @@ def _repack_stale(owners, tables, prepare=False):
         if table is None:
             if capturing:
                 continue
-            if "job_bytes" not in tables:
-                import ctypes
-                nb = ctypes.c_size_t()
-                _lib.check(_lib.load().gmz_conv3x3_pack_job_bytes(ctypes.byref(nb)))
-                if nb.value != _PACK_JOB.itemsize:
-                    raise _lib.GmzError("gmz_conv3x3_pack_job_bytes: %d, expected %d" % (nb.value, _PACK_JOB.itemsize))
-                tables["job_bytes"] = nb.value
+            nb = _lib.query("gmz_conv3x3_pack_job_bytes")
+            if nb != _PACK_JOB.itemsize:
+                raise _lib.GmzError("gmz_conv3x3_pack_job_bytes: %d, expected %d" % (nb, _PACK_JOB.itemsize))
             arr = np.zeros(len(js), dtype=_PACK_JOB)
             for i, (_, _, h) in enumerate(js):
                 arr[i] = (h[2].data_ptr(), h[2].stride(), h[1].data_ptr(), h[3], 0)
@@ -654,14 +600,11 @@ def _repack_stale(owners, tables, prepare=False):
             tables[sig] = table
         if prepare:
             continue
-        _lib.check(_lib.load().gmz_conv3x3_pack_many(_CONV_DTYPES[dtype], _lib.ptr(table), len(js), _lib.stream_ptr()))
+        _lib.call("gmz_conv3x3_pack_many", _CONV_DTYPES[dtype], table, len(js), _lib.stream_ptr())
         for owner, key, h in js:
             owner.__dict__["_gmz_pack"][key] = (owner._version,) + tuple(h[1:])
         n += len(js)
     return n
-
-
-_STATS_SLOTS = {}
 
 
 def _conv3x3_hip(x, packed, mask=None, stats=None, addend=None, bnb=None, bn_y=None, pend=None):
@@ -670,30 +613,22 @@ def _conv3x3_hip(x, packed, mask=None, stats=None, addend=None, bnb=None, bn_y=N
     (_PendingBN), applied and written by this conv's prologue."""
     from . import _lib
     y = torch.empty_like(x, memory_format=torch.channels_last)
+    dt, H, N, stream = _CONV_DTYPES[x.dtype], x.shape[2], x.shape[0], _lib.stream_ptr()
     if pend is not None:
-        _lib.check(_lib.load().gmz_conv3x3_forward_bnapply(
-            _CONV_DTYPES[x.dtype], x.shape[2], _lib.ptr(pend.z), _lib.ptr(pend.res), _lib.ptr(pend.gamma),
-            _lib.ptr(pend.beta), _lib.ptr(pend.save), int(pend.relu), _lib.ptr(x), _lib.ptr(packed), _lib.ptr(y),
-            x.shape[0], _lib.ptr(mask), _lib.ptr(stats), _stats_slots_of(stats), _lib.stream_ptr()))
-        return y
-    if bnb is not None:
-        if addend is not None:
-            addend = addend.to(x.dtype).contiguous(memory_format=torch.channels_last)
-        st, ns = _conv_stats_buffer(x.shape[0], x.device)
-        _lib.check(_lib.load().gmz_conv3x3_forward_bwdstats(
-            _CONV_DTYPES[x.dtype], x.shape[2], _lib.ptr(x), _lib.ptr(packed), _lib.ptr(addend), _lib.ptr(y), x.shape[0],
-            _lib.ptr(bnb.mask), _lib.ptr(bnb.x), _lib.ptr(bn_y), _lib.ptr(bnb.save), int(bnb.relu), _lib.ptr(st),
-            _stats_slots_of(st), _lib.stream_ptr()))
-        bnb.bwd = (st, ns, y)
+        _lib.call("gmz_conv3x3_forward_bnapply", dt, H, pend.z, pend.res, pend.gamma, pend.beta, pend.save,
+                  int(pend.relu), x, packed, y, N, mask, stats, _stats_slots_of(stats), stream)
         return y
     if addend is not None:  # y = round(conv + addend) (the residual gradient folded into the input gradient)
         addend = addend.to(x.dtype).contiguous(memory_format=torch.channels_last)
-        _lib.check(_lib.load().gmz_conv3x3_forward_add(_CONV_DTYPES[x.dtype], x.shape[2], _lib.ptr(x), _lib.ptr(packed),
-                                                       _lib.ptr(addend), _lib.ptr(y), x.shape[0], _lib.stream_ptr()))
-        return y
-    _lib.check(_lib.load().gmz_conv3x3_forward_stats(_CONV_DTYPES[x.dtype], x.shape[2], _lib.ptr(x), _lib.ptr(packed),
-                                                     _lib.ptr(y), x.shape[0], _lib.ptr(mask), _lib.ptr(stats),
-                                                     _stats_slots_of(stats), _lib.stream_ptr()))
+    if bnb is not None:
+        st, ns = _conv_stats_buffer(N, x.device)
+        _lib.call("gmz_conv3x3_forward_bwdstats", dt, H, x, packed, addend, y, N, bnb.mask, bnb.x, bn_y, bnb.save,
+                  int(bnb.relu), st, _stats_slots_of(st), stream)
+        bnb.bwd = (st, ns, y)
+    elif addend is not None:
+        _lib.call("gmz_conv3x3_forward_add", dt, H, x, packed, addend, y, N, stream)
+    else:
+        _lib.call("gmz_conv3x3_forward_stats", dt, H, x, packed, y, N, mask, stats, _stats_slots_of(stats), stream)
     return y
 
 
@@ -728,7 +663,6 @@ HIP_WGRAD = True
 # nothing else reads): the HIP weight gradients then add straight into .grad and return None to
 # autograd.  Every other caller (torch.autograd.grad, hooks, other reducers) gets them through autograd.
 _DIRECT_GRAD = [False]
-_WGRAD_WS = {}
 
 
 # the 3x3 weight gradients of Trainer's backward deferred to its end: one multi-segment launch per weight
@@ -742,7 +676,6 @@ def flush_wgrads():
     """Run the deferred weight gradients (DEFER_WGRAD) into their parameters' f32 .grad."""
     import ctypes
     from . import _lib
-    L = _lib.load()
     for w, uses in _PENDING_WGRAD.items():
         groups = {}
         for x, gy in uses:
@@ -750,47 +683,35 @@ def flush_wgrads():
         for (N, dt, H), lst in groups.items():
             for i in range(0, len(lst), 8):
                 seg = lst[i:i + 8]
-                n = len(seg) * N
-                if n not in _WGRAD_WS:
-                    nb = ctypes.c_size_t()
-                    _lib.check(L.gmz_conv3x3_wgrad_workspace_bytes(n, ctypes.byref(nb)))
-                    _WGRAD_WS[n] = nb.value
-                ws = torch.empty(_WGRAD_WS[n] // 4, dtype=torch.float32, device=w.device)
+                ws = _wgrad_workspace(len(seg) * N, w.device)
                 xs = (ctypes.c_void_p * len(seg))(*[x.data_ptr() for x, _ in seg])
                 gs = (ctypes.c_void_p * len(seg))(*[g.data_ptr() for _, g in seg])
-                st = w.grad.stride()
-                _lib.check(L.gmz_conv3x3_wgrad_segments(_CONV_DTYPES[dt], H, ctypes.cast(xs, ctypes.c_void_p),
-                                                        ctypes.cast(gs, ctypes.c_void_p), len(seg), N,
-                                                        _lib.ptr(w.grad), st[0], st[1], st[2], st[3], 1, _lib.ptr(ws),
-                                                        _lib.nbytes(ws), _lib.stream_ptr()))
+                _lib.call("gmz_conv3x3_wgrad_segments", _CONV_DTYPES[dt], H, ctypes.cast(xs, ctypes.c_void_p),
+                          ctypes.cast(gs, ctypes.c_void_p), len(seg), N, w.grad, *w.grad.stride(), 1, ws,
+                          _lib.nbytes(ws), _lib.stream_ptr())
     _PENDING_WGRAD.clear()
+
+
+def _wgrad_workspace(boards, device):
+    from . import _lib
+    nb = _lib.query("gmz_conv3x3_wgrad_workspace_bytes", boards)
+    return torch.empty(nb // 4, dtype=torch.float32, device=device)
 
 
 def _conv3x3_wgrad_hip(x, gy, grad):
     """grad (f32, any strides) += weight gradient of the 128->128 conv from channels-last x, gy."""
-    import ctypes
     from . import _lib
-    L = _lib.load()
     N = x.shape[0]
-    if N not in _WGRAD_WS:
-        n = ctypes.c_size_t()
-        _lib.check(L.gmz_conv3x3_wgrad_workspace_bytes(N, ctypes.byref(n)))
-        _WGRAD_WS[N] = n.value
-    ws = torch.empty(_WGRAD_WS[N] // 4, dtype=torch.float32, device=x.device)
-    s = grad.stride()
-    _lib.check(L.gmz_conv3x3_wgrad(_CONV_DTYPES[x.dtype], x.shape[2], _lib.ptr(x), _lib.ptr(gy), N, _lib.ptr(grad),
-                                   s[0], s[1], s[2], s[3], 1, _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr()))
+    ws = _wgrad_workspace(N, x.device)
+    _lib.call("gmz_conv3x3_wgrad", _CONV_DTYPES[x.dtype], x.shape[2], x, gy, N, grad, *grad.stride(), 1, ws,
+              _lib.nbytes(ws), _lib.stream_ptr())
 
 
 def _conv_stats_buffer(N, device):
     """f64 [128][slots][3] partials (channel-major) for gmz_conv3x3_forward_stats -> (tensor, slots)."""
     import ctypes
     from . import _lib
-    if N not in _STATS_SLOTS:
-        n = ctypes.c_int()
-        _lib.check(_lib.load().gmz_conv3x3_stats_slots(N, ctypes.byref(n)))
-        _STATS_SLOTS[N] = n.value
-    ns = _STATS_SLOTS[N]
+    ns = _lib.query("gmz_conv3x3_stats_slots", N, ctype=ctypes.c_int)
     return torch.empty(ns * 128 * 3, dtype=torch.float64, device=device), ns
 
 
@@ -888,10 +809,9 @@ class _DynStemHIP(torch.autograd.Function):
         if a32.numel() != h.shape[0]:
             raise RuntimeError("_DynStemHIP: one action per board")
         y = torch.empty_like(h, memory_format=torch.channels_last)
-        _lib.check(_lib.load().gmz_conv3x3_forward_stamp(
-            _CONV_DTYPES[dt], H, _lib.ptr(h), _lib.ptr(_packed_conv_weight(W[:, :128], dt, 0, parent=W)), _lib.ptr(y), n,
-            _lib.ptr(mask), _lib.ptr(stats), _stats_slots_of(stats), _lib.ptr(a32), _lib.ptr(table),
-            _TABLE_DTYPES[table.dtype], _lib.nbytes(table), _lib.stream_ptr()))
+        _lib.call("gmz_conv3x3_forward_stamp", _CONV_DTYPES[dt], H, h, _packed_conv_weight(W[:, :128], dt, 0, parent=W),
+                  y, n, mask, stats, _stats_slots_of(stats), a32, table, _TABLE_DTYPES[table.dtype], _lib.nbytes(table),
+                  _lib.stream_ptr())
         ctx.save_for_backward(h, W, w_emb, a32)
         return y
 
@@ -940,14 +860,23 @@ class _DynStemHIP(torch.autograd.Function):
         return gh, gW, gemb, None, None, None
 
 
+def _hip_conv_dtype(conv, x, cin=128, sizes=None):
+    """The 16-bit dtype in which the HIP 128 -> 128 3x3 kernels (gmz_conv3x3_*) would run ``conv`` on x, or None
+    when they do not cover the case: FUSED_CONV on; a square 4-D GPU activation with 128 channels at a board size
+    of ``sizes`` (HIP_CONV_SIZES); a [128, cin, 3, 3] weight and no bias; f16 or bf16 as the autocast dtype (x's own
+    outside autocast); x channels-last.  The one statement of that condition: _conv3_apply runs what
+    _conv_takes_pending promised on it."""
+    if not (FUSED_CONV and x.is_cuda and x.dim() == 4 and x.shape[1] == 128 and x.shape[2] == x.shape[3]
+            and x.shape[2] in (HIP_CONV_SIZES if sizes is None else sizes)
+            and conv.weight.shape == (128, cin, 3, 3) and conv.bias is None):
+        return None
+    dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+    return dt if (dt in _CONV_DTYPES and x.is_contiguous(memory_format=torch.channels_last)) else None
+
+
 def _dyn_stem_hip_ok(dyn, h):
-    if not (DYN_STEM_HIP and FUSED_CONV and h.is_cuda and h.dim() == 4 and h.shape[1] == 128
-            and h.shape[2] == h.shape[3] and h.shape[2] in (9, 15)):
-        return False
-    if dyn.conv.weight.shape != (128, 128 + dyn.EMB, 3, 3) or dyn.conv.bias is not None:
-        return False
-    dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else h.dtype
-    return dt in _CONV_DTYPES and h.is_contiguous(memory_format=torch.channels_last)
+    """The 144-channel stem (its 128 hidden planes on the HIP conv, the action planes as a stamp) at 9 and 15 only."""
+    return DYN_STEM_HIP and _hip_conv_dtype(dyn.conv, h, cin=128 + dyn.EMB, sizes=(9, 15)) is not None
 
 
 def _conv3(cin, cout):
@@ -959,45 +888,40 @@ def _conv3_apply(conv, x, bn=None, mask=None, link=None, segments=1):
     training-mode BatchNorm that consumes the output — the kernel's epilogue then also reduces its
     (row-masked) statistics, attached to the output for ``_bn_act`` (no separate reduction pass).
     ``segments`` > 1 (no_grad only): the statistics partials per board, for the segmented BatchNorm."""
-    if (FUSED_CONV and x.is_cuda and x.dim() == 4 and x.shape[1] == 128 and x.shape[2] == x.shape[3]
-            and x.shape[2] in HIP_CONV_SIZES and conv.weight.shape == (128, 128, 3, 3) and conv.bias is None):
-        dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
-        if (segments > 1 and dt in _CONV_DTYPES and x.is_contiguous(memory_format=torch.channels_last)
-                and not torch.is_grad_enabled()):
-            from . import _lib
-            xin = x.to(dt)
-            N = xin.shape[0]
-            y = torch.empty_like(xin, memory_format=torch.channels_last)
-            packed = _packed_conv_weight(conv.weight, dt, 0)
-            if bn is not None and bn.training and FUSED_BN:
-                st = torch.empty(128 * N * 3, dtype=torch.float64, device=x.device)
-                m = None if mask is None else mask.contiguous().view(torch.uint8)
-                _lib.check(_lib.load().gmz_conv3x3_forward_board_stats(_CONV_DTYPES[dt], xin.shape[2], _lib.ptr(xin),
-                                                                       _lib.ptr(packed), _lib.ptr(y), N, _lib.ptr(m),
-                                                                       _lib.ptr(st), N, _lib.stream_ptr()))
-                y._gmz_bnstats = (st, "board")
-            else:
-                _lib.check(_lib.load().gmz_conv3x3_forward(_CONV_DTYPES[dt], xin.shape[2], _lib.ptr(xin), _lib.ptr(packed),
-                                                           _lib.ptr(y), N, _lib.stream_ptr()))
-            return y
-        if dt in _CONV_DTYPES and x.is_contiguous(memory_format=torch.channels_last):
-            st = None
-            if bn is not None and bn.training and FUSED_BN:
-                st = _conv_stats_buffer(x.shape[0], x.device)
+    dt = _hip_conv_dtype(conv, x)
+    if dt is not None and segments > 1 and not torch.is_grad_enabled():
+        from . import _lib
+        xin = x.to(dt)
+        N, H = xin.shape[0], xin.shape[2]
+        y = torch.empty_like(xin, memory_format=torch.channels_last)
+        packed = _packed_conv_weight(conv.weight, dt, 0)
+        if bn is not None and bn.training and FUSED_BN:
+            st = torch.empty(128 * N * 3, dtype=torch.float64, device=x.device)
             m = None if mask is None else mask.contiguous().view(torch.uint8)
-            xin = x.to(dt)
-            bnsrc = getattr(xin, "_gmz_bnsrc", None) if xin is x else None  # x = a BatchNorm's output, as is
-            pend = getattr(x, "_gmz_pending", None)
-            if pend is not None:  # x is written by this conv's prologue (once: later readers see it written)
-                if xin is not x:
-                    raise RuntimeError("_conv3_apply: a deferred BatchNorm output needs a conv of its own dtype")
-                x._gmz_pending = None
-            y = _Conv3x3NHWC.apply(xin, conv.weight, m, None if st is None else st[0], link, bnsrc, pend)
-            if link is not None:
-                link.xin = xin
-            if st is not None:
-                y._gmz_bnstats = st
-            return y
+            _lib.call("gmz_conv3x3_forward_board_stats", _CONV_DTYPES[dt], H, xin, packed, y, N, m, st, N,
+                      _lib.stream_ptr())
+            y._gmz_bnstats = (st, "board")
+        else:
+            _lib.call("gmz_conv3x3_forward", _CONV_DTYPES[dt], H, xin, packed, y, N, _lib.stream_ptr())
+        return y
+    if dt is not None:
+        st = None
+        if bn is not None and bn.training and FUSED_BN:
+            st = _conv_stats_buffer(x.shape[0], x.device)
+        m = None if mask is None else mask.contiguous().view(torch.uint8)
+        xin = x.to(dt)
+        bnsrc = getattr(xin, "_gmz_bnsrc", None) if xin is x else None  # x = a BatchNorm's output, as is
+        pend = getattr(x, "_gmz_pending", None)
+        if pend is not None:  # x is written by this conv's prologue (once: later readers see it written)
+            if xin is not x:
+                raise RuntimeError("_conv3_apply: a deferred BatchNorm output needs a conv of its own dtype")
+            x._gmz_pending = None
+        y = _Conv3x3NHWC.apply(xin, conv.weight, m, None if st is None else st[0], link, bnsrc, pend)
+        if link is not None:
+            link.xin = xin
+        if st is not None:
+            y._gmz_bnstats = st
+        return y
     if getattr(x, "_gmz_pending", None) is not None:
         raise RuntimeError("_conv3_apply: a deferred BatchNorm output reached a conv that cannot apply it")
     return conv(x)
@@ -1064,25 +988,21 @@ def _headconv_forward(x, w0, b0, w1, b1):
     """gmz_head_conv1x1_forward of the channels-last x: (y0, y1) channels-last [n, O, H, W] and what the backward
     needs"""
     from . import _lib
-    L = _lib.load()
     n, C, H, W = x.shape
     O0, O1 = w0.shape[0], w1.shape[0]
     P = n * H * W
     wm = [_head_param(t, (O0, C)) for t in (w0, b0, w1, b1)]  # [O][C] rows / [O]: f32, contiguous views
     y0 = torch.empty((n, H, W, O0), dtype=x.dtype, device=x.device)
     y1 = torch.empty((n, H, W, O1), dtype=x.dtype, device=x.device)
-    _lib.check(L.gmz_head_conv1x1_forward(_BN_DTYPES[x.dtype], _lib.ptr(x), P, C, _lib.ptr(wm[0]), _lib.ptr(wm[1]),
-                                          O0, _lib.ptr(wm[2]), _lib.ptr(wm[3]), O1, _lib.ptr(y0), _lib.ptr(y1),
-                                          _lib.stream_ptr()))
+    _lib.call("gmz_head_conv1x1_forward", _BN_DTYPES[x.dtype], x, P, C, wm[0], wm[1], O0, wm[2], wm[3], O1, y0, y1,
+              _lib.stream_ptr())
     return y0.permute(0, 3, 1, 2), y1.permute(0, 3, 1, 2), (wm[0], wm[2], (O0, O1))
 
 
 def _headconv_backward(x, saved, params, g0, g1):
     """gmz_head_conv1x1_backward: (dx channels-last like x, the four parameter gradients — None when they went
     straight into the trainer's f32 .grad, _DIRECT_GRAD)"""
-    import ctypes
     from . import _lib
-    L = _lib.load()
     w0m, w1m, (O0, O1) = saved
     n, C, H, W = x.shape
     P = n * H * W
@@ -1091,16 +1011,14 @@ def _headconv_backward(x, saved, params, g0, g1):
     g0 = g0.to(x.dtype).permute(0, 2, 3, 1).contiguous()  # [n, H, W, O]: positions x outputs
     g1 = g1.to(x.dtype).permute(0, 2, 3, 1).contiguous()
     dx = torch.empty_like(x)  # channels-last like x
-    nb = ctypes.c_size_t()
-    _lib.check(L.gmz_head_conv1x1_workspace_bytes(P, O0 + O1, ctypes.byref(nb)))
-    ws = torch.empty(nb.value // 4, dtype=torch.float32, device=x.device)
+    ws = torch.empty(_lib.query("gmz_head_conv1x1_workspace_bytes", P, O0 + O1) // 4, dtype=torch.float32,
+                     device=x.device)
     # the trainer's own backward (_DIRECT_GRAD): add into the f32 .grad views of its flat bucket
     direct = _DIRECT_GRAD[0] and all(p.grad is not None and p.grad.dtype == torch.float32
                                      and p.grad.is_contiguous() for p in params)
     outs = [p.grad if direct else torch.empty(p.shape, dtype=torch.float32, device=x.device) for p in params]
-    _lib.check(L.gmz_head_conv1x1_backward(_BN_DTYPES[x.dtype], _lib.ptr(x), P, C, _lib.ptr(w0m), O0, _lib.ptr(w1m), O1,
-                                           _lib.ptr(g0), _lib.ptr(g1), _lib.ptr(dx), *[_lib.ptr(t) for t in outs],
-                                           int(direct), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr()))
+    _lib.call("gmz_head_conv1x1_backward", _BN_DTYPES[x.dtype], x, P, C, w0m, O0, w1m, O1, g0, g1, dx, *outs,
+              int(direct), ws, _lib.nbytes(ws), _lib.stream_ptr())
     if direct:
         return dx, [None] * 4
     return dx, [t.to(p.dtype) for t, p in zip(outs, params)]
@@ -1274,8 +1192,7 @@ class _BigKLinear(torch.autograd.Function):
                 from . import _lib
                 C, HW = ctx.perm
                 dst = w.grad if acc else torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-                _lib.check(_lib.load().gmz_grad_add_t(_BN_DTYPES[gwt.dtype], _lib.ptr(gwt), HW, C, O, _lib.ptr(dst),
-                                                     _lib.stream_ptr()))
+                _lib.call("gmz_grad_add_t", _BN_DTYPES[gwt.dtype], gwt, HW, C, O, dst, _lib.stream_ptr())
                 if not acc:
                     gw = dst
         gb = gy.sum(0, dtype=torch.float32) if ctx.needs_input_grad[2] else None
@@ -1336,8 +1253,7 @@ def _bigk2_backward(xs, ws, w1, w2, perm, g1, g2, needs, gx_acc=None):
             from . import _lib
             C, HW = perm
             dst = w.grad if acc else torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-            _lib.check(_lib.load().gmz_grad_add_t_cols(_BN_DTYPES[gwt.dtype], _lib.ptr(gwt), HW, C, O, O1 + O2, c0,
-                                                      _lib.ptr(dst), _lib.stream_ptr()))
+            _lib.call("gmz_grad_add_t_cols", _BN_DTYPES[gwt.dtype], gwt, HW, C, O, O1 + O2, c0, dst, _lib.stream_ptr())
             if not acc:
                 outs[2 * i] = dst
     if needs[2] or needs[4]:
@@ -1703,17 +1619,12 @@ SEG_BN_HIP_MIN_C = 64
 # workgroups over every channel instead of one workgroup per channel (SEG_BN_SMALL; False: PyTorch's _bn_seg_grad)
 SEG_BN_SMALL = True
 _SEG_BN_SMALL_C = 8
-_SBS_WS = {}
 
 
 def _seg_bn_small_ws(nseg, C, device):
-    import ctypes
     from . import _lib
-    if nseg not in _SBS_WS:
-        n = ctypes.c_size_t()
-        _lib.check(_lib.load().gmz_seg_bn_small_workspace_bytes(nseg, C, ctypes.byref(n)))
-        _SBS_WS[nseg] = n.value
-    return torch.empty((_SBS_WS[nseg] + 7) // 8, dtype=torch.float64, device=device)
+    n = _lib.query("gmz_seg_bn_small_workspace_bytes", nseg, C)
+    return torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
 
 
 class _SegBN(torch.autograd.Function):
@@ -1730,18 +1641,13 @@ class _SegBN(torch.autograd.Function):
         else:
             y = torch.empty((N, C), dtype=torch.float32, device=x.device)
         st = torch.empty(3 * nseg * C + nseg, dtype=torch.float32, device=x.device)
+        args = (_BN_DTYPES[x.dtype], x, m, nseg, N // nseg, S, C, gamma, beta, float(eps), y, st, _lib.nbytes(st),
+                int(update), float(momentum), rmean, rvar, nbt, pre)
         if C <= _SEG_BN_SMALL_C:  # few channels: (segment, chunk) workgroups over every channel
             ws = _seg_bn_small_ws(nseg, C, x.device)
-            _lib.check(_lib.load().gmz_seg_bn_forward_small(
-                _BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(m), nseg, N // nseg, S, C, _lib.ptr(gamma), _lib.ptr(beta),
-                float(eps), _lib.ptr(y), _lib.ptr(st), _lib.nbytes(st), int(update), float(momentum), _lib.ptr(rmean),
-                _lib.ptr(rvar), _lib.ptr(nbt), _lib.ptr(pre), _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr()))
+            _lib.call("gmz_seg_bn_forward_small", *args, ws, _lib.nbytes(ws), _lib.stream_ptr())
         else:
-            _lib.check(_lib.load().gmz_seg_bn_forward(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(m), nseg, N // nseg, S, C,
-                                                      _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(y),
-                                                      _lib.ptr(st), _lib.nbytes(st), int(update), float(momentum),
-                                                      _lib.ptr(rmean), _lib.ptr(rvar), _lib.ptr(nbt), _lib.ptr(pre),
-                                                      _lib.stream_ptr()))
+            _lib.call("gmz_seg_bn_forward", *args, _lib.stream_ptr())
         ctx.save_for_backward(x, gamma, beta, st, m)
         ctx.nseg = nseg
         ctx.mark_non_differentiable(st)
@@ -1761,17 +1667,13 @@ class _SegBN(torch.autograd.Function):
                   and gamma.grad.is_contiguous() and beta.grad.is_contiguous())
         dg = gamma.grad if direct else torch.empty(C, dtype=torch.float32, device=x.device)
         db = beta.grad if direct else torch.empty(C, dtype=torch.float32, device=x.device)
+        args = (_BN_DTYPES[x.dtype], x, dy, m, ctx.nseg, N // ctx.nseg, S, C, gamma, st, _lib.nbytes(st), dx, dg, db,
+                int(direct))
         if C <= _SEG_BN_SMALL_C:
             ws = _seg_bn_small_ws(ctx.nseg, C, x.device)
-            _lib.check(_lib.load().gmz_seg_bn_backward_small(
-                _BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(dy), _lib.ptr(m), ctx.nseg, N // ctx.nseg, S, C,
-                _lib.ptr(gamma), _lib.ptr(st), _lib.nbytes(st), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), int(direct),
-                _lib.ptr(ws), _lib.nbytes(ws), _lib.stream_ptr()))
+            _lib.call("gmz_seg_bn_backward_small", *args, ws, _lib.nbytes(ws), _lib.stream_ptr())
         else:
-            _lib.check(_lib.load().gmz_seg_bn_backward(_BN_DTYPES[x.dtype], _lib.ptr(x), _lib.ptr(dy), _lib.ptr(m),
-                                                       ctx.nseg, N // ctx.nseg, S, C, _lib.ptr(gamma), _lib.ptr(st),
-                                                       _lib.nbytes(st), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db),
-                                                       int(direct), _lib.stream_ptr()))
+            _lib.call("gmz_seg_bn_backward", *args, _lib.stream_ptr())
         if direct:
             return dx, None, None, None, None, None, None, None, None, None, None, None
         return dx, dg, db, None, None, None, None, None, None, None, None, None
@@ -1894,6 +1796,175 @@ def _side_streams(device):
     return _SIDE_STREAMS[device]
 
 
+@torch.no_grad()
+def _target_values(target_model, obs, rew, mval, cfg):
+    """z [B, U+1] (loss.py:53-65) on the current stream: the n-step value targets, bootstrapped from the target
+    network's value of the last observation (loss.py:54-55)."""
+    last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16 and not TARGET_SPLIT, split=TARGET_SPLIT)[:, 0]
+    return value_targets(rew, mval, last_v, cfg)
+
+
+class _ConsistencyStates:
+    """The no-grad representations of obs[1..U] whose projections are the consistency targets (loss.py:102-104),
+    made the way the switches say: on the stream ``side`` (CONCURRENT_FORWARD's side stream 1, forked from ``main``)
+    or on the current one; as one segmented pass (BATCHED_CONSISTENCY) or step by step; with neither, each step
+    lazily at its use.  Always in step order after obs[0]'s representation, so the representation BatchNorms'
+    running statistics update in the reference's order.  ``step`` and ``stacked`` hand the states out safe to use
+    on ``main``: every wait on side's events and every record_stream of these tensors is in here."""
+
+    def __init__(self, model, obs, masks, main=None, side=None):
+        self.model, self.obs, self.masks, self.main, self.side = model, obs, masks, main, side
+        self.states = self.events = None
+        U = len(masks)
+        batched = BATCHED_CONSISTENCY and U > 1
+        if side is not None:
+            side.wait_stream(main)
+            with torch.cuda.stream(side), torch.no_grad():
+                if batched:
+                    self.states = consistency_representations(model, obs, masks)
+                    self.events = [self._recorded()] * U
+                else:
+                    self.states, self.events = [], []
+                    for s in range(U):
+                        self.states.append(self._represent(s))
+                        self.events.append(self._recorded())
+        elif batched:  # one stream: the batched pass right after obs[0]'s
+            with torch.no_grad():
+                self.states = consistency_representations(model, obs, masks)
+
+    def _represent(self, s):
+        return self.model.representation(self.obs[:, s + 1], mask=self.masks[s])
+
+    def _recorded(self):
+        ev = torch.cuda.Event()
+        ev.record(self.side)
+        return ev
+
+    @torch.no_grad()
+    def step(self, s):
+        """The state of step s, safe to use on the current stream."""
+        if self.states is None:
+            return self._represent(s)
+        if self.side is not None:
+            self.main.wait_event(self.events[s])
+            self.states[s].record_stream(self.main)
+        return self.states[s]
+
+    @torch.no_grad()
+    def stacked(self):
+        """All U steps as one step-major tensor [U*B, ...], safe to use on the current stream."""
+        states = self.states
+        if states is None:
+            states = [self._represent(s) for s in range(len(self.masks))]
+        elif self.side is not None:
+            self.main.wait_event(self.events[-1])
+        th = getattr(states, "stacked", None)
+        if self.side is not None:
+            # every per-step state made on the side stream is consumed on main (by the cat, or as th itself): each is
+            # recorded on main so none returns to the side stream's pool while main's use is still queued (ADVICE r5)
+            for t in states:
+                t.record_stream(self.main)
+        if th is None:
+            th = states[0] if len(states) == 1 else torch.cat(states)
+        if self.side is not None:
+            th.record_stream(self.main)
+        return th
+
+
+def _step0_terms(pl, vl, pi, zsup, z, vsup):
+    """Step 0's policy and value cross-entropies per row and |value error| (the new PER priorities)."""
+    lp = F.cross_entropy(pl.float(), pi[:, 0], reduction="none")
+    lv = F.cross_entropy(vl.float(), zsup[0], reduction="none")
+    # loss.py:78 passes softmax(logits) to support_to_scalar, which applies softmax again:
+    # the PER priority is computed from that doubly-softmaxed value (kept as the reference does)
+    v0 = support_to_scalar(F.softmax(vl.float(), dim=1), *vsup)
+    td = (v0.detach()[:, 0] - z[:, 0]).abs()
+    return lp, lv, td
+
+
+def _stacked_step_terms(lp, lv, ms, pls, vls, rls, dyns, trus, pi, zsup, rsupt, lam, zero):
+    """The U unroll steps' cross-entropies and consistency losses as one call each over the stacked [U, B, .] head
+    outputs (masked rows zeroed, summed over the steps): the same per-row values as the per-step calls
+    (_per_step_terms), ~5x fewer kernels in the forward and the backward.  ``lp``, ``lv``: step 0's policy and value
+    terms, ``zero``: a 0-dim zero; returns (lp, lv with the steps' terms added, the reward term, the consistency
+    loss)."""
+    U, B = ms.shape
+
+    def ce(logits, target):
+        x = logits.float().reshape(U * B, -1)
+        return F.cross_entropy(x, target.reshape(U * B, -1), reduction="none").view(U, B)
+    lp = lp + torch.where(ms, ce(pls, pi[:, 1:].transpose(0, 1)), zero).sum(0)
+    lv = lv + torch.where(ms, ce(vls, zsup[1:]), zero).sum(0)
+    lr_ = torch.where(ms, ce(rls, rsupt), zero).sum(0)
+    live_s = ms.any(1).to(torch.float32)
+    cons = (live_s * barlow_loss_steps(dyns, trus, lam, ms)).sum()
+    return lp, lv, lr_, cons
+
+
+def _per_step_terms(lp, lv, ms, pls, vls, rls, dyns, trus, pi, zsup, rsupt, lam, zero):
+    """_stacked_step_terms step by step, over lists of U per-step tensors (BATCHED_LOSS off, A/B): each step's terms
+    added in step order."""
+    lr_, cons = torch.zeros(lp.shape[0], device=lp.device), zero
+    for s, m in enumerate(ms):
+        lp = lp + torch.where(m, F.cross_entropy(pls[s].float(), pi[:, s + 1], reduction="none"), zero)
+        lv = lv + torch.where(m, F.cross_entropy(vls[s].float(), zsup[s + 1], reduction="none"), zero)
+        lr_ = lr_ + torch.where(m, F.cross_entropy(rls[s].float(), rsupt[s], reduction="none"), zero)
+        live = m.any().to(torch.float32)   # 0: the reference's `continue` (loss.py:90-91)
+        cons = cons + live * barlow_loss(dyns[s], trus[s], lam, m)
+    return lp, lv, lr_, cons
+
+
+def _unroll_heads_stacked(model, h, act_aug, live_act, consistency):
+    """BATCHED_HEADS: the unroll's dynamics chain first (trunks only), then every head over the stacked steps.
+    Returns (step 0's policy and value logits, the number of steps with a live row, (ms, pls, vls, rls, dyns, trus):
+    the U steps' row masks [U, B] and policy, value, reward logits, dynamics and target projections [U, B, .])."""
+    U, B = live_act.shape
+    h0, hks, mks = h, [], []
+    a_all = torch.where(live_act, act_aug.t(), torch.zeros_like(act_aug.t())).reshape(-1)  # step-major [U*B]
+    dyn_net = model.dynamics_net
+    emb_all = None if _dyn_stem_hip_ok(dyn_net, h) else dyn_net.embed(a_all, h)  # every step's embedding
+    # a step with no live row counts nothing (loss.py:90-91); a count of 0/1 terms: exact in any order
+    steps = live_act.any(1).to(torch.float32).sum()
+    for s in range(U):
+        m, rows = live_act[s], slice(s * B, (s + 1) * B)
+        hk, _ = model.dynamics(h, a_all[rows], mask=m, reward=False, emb=None if emb_all is None else emb_all[rows])
+        hks.append(hk)
+        mks.append(m)
+        h = _HalveGrad.apply(torch.where(m[:, None, None, None], hk, h))
+    ms = torch.stack(mks)                                      # [U, B]
+    hp = torch.cat([h0] + hks)                                 # [(U+1)B]: step-major, step 0 = obs[0]'s
+    msp = torch.cat((torch.ones_like(ms[:1]), ms))
+    first = _heads_input(model, hp, B)  # the heads' first layers in one node (None: no fused path)
+    pls_all, vls_all = _prediction_seg(model.prediction_net, hp, msp, None if first is None else first[:2])
+    rl_all, dyn_all, sdyn = _reward_projection_seg(model, hp[B:], ms, None if first is None else first[2:])
+    with torch.no_grad():
+        # the projection BatchNorm's running statistics in the reference's order: dynamics s, then target s
+        tru_all = _projection_seg(model.projection_net, consistency.stacked(), ms, sdyn)
+    stacked = tuple(x.view(U, B, -1) for x in (pls_all[B:], vls_all[B:], rl_all, dyn_all, tru_all))
+    return pls_all[:B], vls_all[:B], steps, (ms,) + stacked
+
+
+def _unroll_heads_per_step(model, h, act_aug, live_act, consistency):
+    """The reference's own order (loss.py:70,89-107): every head right after its dynamics step.  Returns what
+    _unroll_heads_stacked returns; with BATCHED_LOSS off the six per-step members are lists of U tensors."""
+    pl, vl = model.prediction(h)
+    per_step = []
+    for s, m in enumerate(live_act):
+        # full-batch step, row-masked BatchNorm statistics and losses (== the reference's
+        # sub-batch h[m] computation, loss.py:89-107, with fixed shapes)
+        hk, rl = model.dynamics(h, torch.where(m, act_aug[:, s], torch.zeros_like(act_aug[:, s])), mask=m)
+        plk, vlk = model.prediction(hk, mask=m)
+        dyn = model.project(hk, with_grad=True, mask=m)
+        with torch.no_grad():
+            tru = model.project(consistency.step(s), with_grad=False, mask=m)
+        per_step.append((m, plk, vlk, rl, dyn, tru))
+        h = _HalveGrad.apply(torch.where(m[:, None, None, None], hk, h))
+    members = tuple(zip(*per_step)) if per_step else ((),) * 6
+    if BATCHED_LOSS and per_step:
+        members = tuple(torch.stack(x) for x in members)
+    return pl, vl, live_act.any(1).to(torch.float32).sum(), members
+
+
 def muzero_loss(model, target_model, batch, is_weights, cfg, k=None, flip=None, amp=False, amp_dtype=None,
                 sync_logs=True, augmented=False):
     """loss.py:30-158.  ``batch`` = (obs [B,U+1,3,H,W], actions [B,U], rewards [B,U],
@@ -1919,177 +1990,38 @@ def muzero_loss(model, target_model, batch, is_weights, cfg, k=None, flip=None, 
         obs, pi, act_aug = augment(obs, pi, act, k, flip)
     model.train()
     target_model.eval()
-    c, W = cfg, cfg.LOSS_WEIGHTS
+    c, W, U = cfg, cfg.LOSS_WEIGHTS, cfg.NUM_UNROLL_STEPS
     vsup = (c.VALUE_SUPPORT_MIN, c.VALUE_SUPPORT_MAX, c.VALUE_SUPPORT_BINS)
     rsup = (c.REWARD_SUPPORT_MIN, c.REWARD_SUPPORT_MAX, c.REWARD_SUPPORT_BINS)
     side = _side_streams(obs.device) if (CONCURRENT_FORWARD and obs.is_cuda) else None
+    main = torch.cuda.current_stream(obs.device) if side is not None else None
     if side is not None:  # the target network's value on side stream 0, from here to its first use
-        main = torch.cuda.current_stream(obs.device)
         side[0].wait_stream(main)
-        with torch.cuda.stream(side[0]), torch.no_grad():
-            last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16 and not TARGET_SPLIT, split=TARGET_SPLIT)[:, 0]
-            z = value_targets(rew, mval, last_v, c)
-    else:
-        with torch.no_grad():
-            last_v = target_model.initial_value(obs[:, -1], f16=TARGET_F16 and not TARGET_SPLIT, split=TARGET_SPLIT)[:, 0]
-            z = value_targets(rew, mval, last_v, c)
+    with torch.cuda.stream(side[0]) if side is not None else contextlib.nullcontext():
+        z = _target_values(target_model, obs, rew, mval, c)
     dev_type = obs.device.type
     zero = torch.zeros((), device=obs.device)
     with torch.autocast(dev_type, enabled=amp and dev_type == "cuda", dtype=amp_dtype or torch.float16,
                         cache_enabled=AUTOCAST_CACHE):
         h = model.representation(obs[:, 0])
-        tru_h = None
-        if side is not None:
-            # the consistency representations of obs[1..U] (no grad) on side stream 1, in step order
-            # after obs[0]'s (the representation BatchNorms' running statistics update in the
-            # reference's order); their projections stay on this stream, interleaved with the dynamics'
-            # projections as in the reference (the projection BatchNorm's running statistics)
-            live_act = (act != -1).t().contiguous()  # [U, B]: each step's mask a contiguous row (2 launches, not U)
-            masks = list(live_act)
-            side[1].wait_stream(main)
-            tru_h, tru_ev = [], []
-            with torch.cuda.stream(side[1]), torch.no_grad():
-                if BATCHED_CONSISTENCY and c.NUM_UNROLL_STEPS > 1:
-                    tru_h = consistency_representations(model, obs, masks)
-                    ev = torch.cuda.Event()
-                    ev.record(side[1])
-                    tru_ev = [ev] * c.NUM_UNROLL_STEPS
-                else:
-                    for s in range(c.NUM_UNROLL_STEPS):
-                        tru_h.append(model.representation(obs[:, s + 1], mask=masks[s]))
-                        ev = torch.cuda.Event()
-                        ev.record(side[1])
-                        tru_ev.append(ev)
+        live_act = (act != -1).t().contiguous()  # [U, B]: each step's mask a contiguous row (2 launches, not U)
+        # the consistency representations of obs[1..U] (no grad) on side stream 1 when there is one; their
+        # projections stay on this stream, interleaved with the dynamics' projections as in the reference (the
+        # projection BatchNorm's running statistics)
+        consistency = _ConsistencyStates(model, obs, list(live_act), main, None if side is None else side[1])
+        if side is not None:  # the target values' first use: z is consumed on main from here on
             main.wait_stream(side[0])
             z.record_stream(main)
-        elif BATCHED_CONSISTENCY and c.NUM_UNROLL_STEPS > 1:  # one stream: the batched pass right after obs[0]'s
-            with torch.no_grad():
-                tru_h = consistency_representations(model, obs, [act[:, s] != -1 for s in range(c.NUM_UNROLL_STEPS)])
-        U = c.NUM_UNROLL_STEPS
-        if BATCHED_HEADS and BATCHED_LOSS and not SUBBATCH_BN and U > 0:
-            # the unroll's dynamics chain first (trunks only), then every head over the stacked steps
-            zsup = scalar_to_support(z.t().contiguous(), *vsup)       # [U+1, B, bins]
-            rsupt = scalar_to_support(rew.t().contiguous(), *rsup)    # [U, B, bins]
-            h0, hks, mks = h, [], []
-            if side is None:
-                live_act = (act != -1).t().contiguous()                 # [U, B]: each step's mask a contiguous row
-            a_all = torch.where(live_act, act_aug.t(), torch.zeros_like(act_aug.t())).reshape(-1)  # step-major [U*B]
-            dyn_net = model.dynamics_net
-            emb_all = None if _dyn_stem_hip_ok(dyn_net, h) else dyn_net.embed(a_all, h)  # every step's embedding
-            B0 = h.shape[0]
-            # a step with no live row counts nothing (loss.py:90-91); a count of 0/1 terms: exact in any order
-            steps = live_act.any(1).to(torch.float32).sum()
-            for s in range(U):
-                m = live_act[s]
-                hk, _ = model.dynamics(h, a_all[s * B0:(s + 1) * B0], mask=m, reward=False,
-                                       emb=None if emb_all is None else emb_all[s * B0:(s + 1) * B0])
-                hks.append(hk)
-                mks.append(m)
-                h = _HalveGrad.apply(torch.where(m[:, None, None, None], hk, h))
-            ms = torch.stack(mks)                                      # [U, B]
-            B = ms.shape[1]
-            hp = torch.cat([h0] + hks)                                 # [(U+1)B]: step-major, step 0 = obs[0]'s
-            pred = model.prediction_net
-            msp = torch.cat((torch.ones_like(ms[:1]), ms))
-            first = _heads_input(model, hp, B)  # the heads' first layers in one node (None: no fused path)
-            pls_all, vls_all = _prediction_seg(pred, hp, msp, None if first is None else first[:2])
-            rl_all, dyn_all, sdyn = _reward_projection_seg(model, hp[B:], ms, None if first is None else first[2:])
-            with torch.no_grad():
-                if tru_h is None:
-                    tru_h = [model.representation(obs[:, s + 1], mask=mks[s]) for s in range(U)]
-                elif side is not None:
-                    main.wait_event(tru_ev[-1])
-                th = getattr(tru_h, "stacked", None)
-                if side is not None:
-                    # every per-step state made on side[1] is consumed on main (by the cat, or as th itself): each
-                    # is recorded on main so none returns to side[1]'s pool while main's use is still queued
-                    for t in tru_h:
-                        t.record_stream(main)
-                if th is None:
-                    th = tru_h[0] if len(tru_h) == 1 else torch.cat(tru_h)
-                if side is not None:
-                    th.record_stream(main)
-                # the projection BatchNorm's running statistics in the reference's order: dynamics s, then target s
-                tru_all = _projection_seg(model.projection_net, th, ms, sdyn)
-            pl, vl = pls_all[:B], vls_all[:B]
-            lp = F.cross_entropy(pl.float(), pi[:, 0], reduction="none")
-            lv = F.cross_entropy(vl.float(), zsup[0], reduction="none")
-            # loss.py:78 passes softmax(logits) to support_to_scalar, which applies softmax again:
-            # the PER priority is computed from that doubly-softmaxed value (kept as the reference does)
-            v0 = support_to_scalar(F.softmax(vl.float(), dim=1), *vsup)
-            td = (v0.detach()[:, 0] - z[:, 0]).abs()
-            pls, vls = pls_all[B:].view(U, B, -1), vls_all[B:].view(U, B, -1)
-            rls, dyns, trus = rl_all.view(U, B, -1), dyn_all.view(U, B, -1), tru_all.view(U, B, -1)
-
-            def ce(logits, target):
-                x = logits.float().reshape(U * B, -1)
-                return F.cross_entropy(x, target.reshape(U * B, -1), reduction="none").view(U, B)
-            lp = lp + torch.where(ms, ce(pls, pi[:, 1:].transpose(0, 1)), zero).sum(0)
-            lv = lv + torch.where(ms, ce(vls, zsup[1:]), zero).sum(0)
-            lr_ = torch.where(ms, ce(rls, rsupt), zero).sum(0)
-            live_s = ms.any(1).to(torch.float32)
-            cons = (live_s * barlow_loss_steps(dyns, trus, c.BARLOW_LAMBDA, ms)).sum()
-        else:
-            pl, vl = model.prediction(h)
-            lp = F.cross_entropy(pl.float(), pi[:, 0], reduction="none")
-            # the support targets of every step in two calls (the per-step calls were ~10 tiny kernels each)
-            # (step-major, so each step's [B, bins] block is contiguous)
-            zsup = scalar_to_support(z.t().contiguous(), *vsup)       # [U+1, B, bins]
-            rsupt = scalar_to_support(rew.t().contiguous(), *rsup)    # [U, B, bins]
-            lv = F.cross_entropy(vl.float(), zsup[0], reduction="none")
-            # loss.py:78 passes softmax(logits) to support_to_scalar, which applies softmax again:
-            # the PER priority is computed from that doubly-softmaxed value (kept as the reference does)
-            v0 = support_to_scalar(F.softmax(vl.float(), dim=1), *vsup)
-            td = (v0.detach()[:, 0] - z[:, 0]).abs()
-            lr_ = torch.zeros(obs.shape[0], device=obs.device)
-            steps = zero
-            cons = zero
-            U = c.NUM_UNROLL_STEPS
-            per_step = []  # BATCHED_LOSS: each step's head outputs, their loss terms taken after the unroll
-            for s in range(U):
-                m = act[:, s] != -1
-                live = m.any().to(torch.float32)   # 0: the reference's `continue` (loss.py:90-91)
-                steps = steps + live
-                # full-batch step, row-masked BatchNorm statistics and losses (== the reference's
-                # sub-batch h[m] computation, loss.py:89-107, with fixed shapes)
-                hk, rl = model.dynamics(h, torch.where(m, act_aug[:, s], torch.zeros_like(act_aug[:, s])), mask=m)
-                plk, vlk = model.prediction(hk, mask=m)
-                if not BATCHED_LOSS:
-                    lp = lp + torch.where(m, F.cross_entropy(plk.float(), pi[:, s + 1], reduction="none"), zero)
-                    lv = lv + torch.where(m, F.cross_entropy(vlk.float(), zsup[s + 1],
-                                                             reduction="none"), zero)
-                    lr_ = lr_ + torch.where(m, F.cross_entropy(rl.float(), rsupt[s],
-                                                               reduction="none"), zero)
-                dyn = model.project(hk, with_grad=True, mask=m)
-                with torch.no_grad():
-                    if tru_h is not None and side is None:
-                        tru = model.project(tru_h[s], with_grad=False, mask=m)
-                    elif tru_h is not None:
-                        main.wait_event(tru_ev[s])
-                        tru_h[s].record_stream(main)
-                        tru = model.project(tru_h[s], with_grad=False, mask=m)
-                    else:
-                        tru = model.project(model.representation(obs[:, s + 1], mask=m), with_grad=False, mask=m)
-                if BATCHED_LOSS:
-                    per_step.append((m, plk, vlk, rl, dyn, tru))
-                else:
-                    cons = cons + live * barlow_loss(dyn, tru, c.BARLOW_LAMBDA, m)
-                h = _HalveGrad.apply(torch.where(m[:, None, None, None], hk, h))
-            if BATCHED_LOSS and U > 0:
-                # the U steps' cross-entropies and consistency losses as one call each over the stacked
-                # [U, B, .] outputs (masked rows zeroed, summed over the steps): the same per-row values as
-                # the per-step calls, ~5x fewer kernels in the forward and the backward
-                ms, pls, vls, rls, dyns, trus = (torch.stack(x) for x in zip(*per_step))
-                B = ms.shape[1]
-
-                def ce(logits, target):
-                    x = logits.float().reshape(U * B, -1)
-                    return F.cross_entropy(x, target.reshape(U * B, -1), reduction="none").view(U, B)
-                lp = lp + torch.where(ms, ce(pls, pi[:, 1:].transpose(0, 1)), zero).sum(0)
-                lv = lv + torch.where(ms, ce(vls, zsup[1:]), zero).sum(0)
-                lr_ = lr_ + torch.where(ms, ce(rls, rsupt), zero).sum(0)
-                live_s = ms.any(1).to(torch.float32)
-                cons = (live_s * barlow_loss_steps(dyns, trus, c.BARLOW_LAMBDA, ms)).sum()
+        # the support targets of every step in two calls (the per-step calls were ~10 tiny kernels each)
+        # (step-major, so each step's [B, bins] block is contiguous)
+        zsup = scalar_to_support(z.t().contiguous(), *vsup)       # [U+1, B, bins]
+        rsupt = scalar_to_support(rew.t().contiguous(), *rsup)    # [U, B, bins]
+        stacked_heads = BATCHED_HEADS and BATCHED_LOSS and not SUBBATCH_BN and U > 0
+        unroll = _unroll_heads_stacked if stacked_heads else _unroll_heads_per_step
+        pl, vl, steps, members = unroll(model, h, act_aug, live_act, consistency)
+        lp, lv, td = _step0_terms(pl, vl, pi, zsup, z, vsup)
+        terms = _stacked_step_terms if (BATCHED_LOSS and U > 0) else _per_step_terms
+        lp, lv, lr_, cons = terms(lp, lv, *members, pi, zsup, rsupt, c.BARLOW_LAMBDA, zero)
     lp = lp / (steps + 1)
     lv = lv / (steps + 1)
     lr_ = lr_ / steps.clamp(min=1.0)
@@ -2379,7 +2311,7 @@ class Trainer:
     def _stamp(self, phase):
         if self._comm_clock is not None:
             from . import _lib
-            _lib.check(_lib.load().gmz_comm_stamp(_lib.ptr(self._comm_clock), phase, _lib.stream_ptr()))
+            _lib.call("gmz_comm_stamp", self._comm_clock, phase, _lib.stream_ptr())
 
     def _allreduce_start(self):
         """Bucket A's all-reduce, issued asynchronously (RCCL on its own stream, after the backward's kernels)."""
@@ -2443,9 +2375,8 @@ class Trainer:
         target twins (a parameter whose twin has other strides gets its soft update from PyTorch)."""
         import ctypes
         from . import _lib
-        L = _lib.load()
         ib, ch, wsb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_size_t()
-        _lib.check(L.gmz_opt_layout(ctypes.byref(ib), ctypes.byref(ch), ctypes.byref(wsb)))
+        _lib.call("gmz_opt_layout", ctypes.byref(ib), ctypes.byref(ch), ctypes.byref(wsb))
         dt = np.dtype([("p", "<u8"), ("t", "<u8"), ("off", "<i8"), ("n", "<i4"), ("pi", "<i4")])
         if ib.value != dt.itemsize:
             raise _lib.GmzError("gmz_opt_layout: item of %d bytes, expected %d" % (ib.value, dt.itemsize))
@@ -2490,11 +2421,10 @@ class Trainer:
             amp = self.scaler.is_enabled()
             scale = self.scaler._scale if amp else None
             b1, b2 = g["betas"]
-            _lib.check(_lib.load().gmz_opt_step(
-                _lib.ptr(f["items"]), f["n_items"], _lib.ptr(self.flat_grad), _lib.ptr(f["m"]), _lib.ptr(f["v"]),
-                self.flat_grad.numel(), _lib.ptr(scale), int(amp), float(c.GRAD_CLIP_NORM), _lib.ptr(g["lr"]),
-                float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(c.TARGET_MODEL_TAU),
-                _lib.ptr(f["step"]), _lib.ptr(f["coef"]), _lib.ptr(f["ws"]), _lib.nbytes(f["ws"]), _lib.stream_ptr()))
+            _lib.call("gmz_opt_step", f["items"], f["n_items"], self.flat_grad, f["m"], f["v"], self.flat_grad.numel(),
+                      scale, int(amp), float(c.GRAD_CLIP_NORM), g["lr"], float(b1), float(b2), float(g["eps"]),
+                      float(g["weight_decay"]), float(c.TARGET_MODEL_TAU), f["step"], f["coef"], f["ws"],
+                      _lib.nbytes(f["ws"]), _lib.stream_ptr())
             if amp:  # GradScaler.update with the step's found_inf
                 torch._amp_update_scale_(self.scaler._scale, self.scaler._growth_tracker, f["coef"][:1],
                                          self.scaler._growth_factor, self.scaler._backoff_factor,

@@ -86,6 +86,41 @@ def test_capacity_arguments_fail_before_any_launch():
     assert "workspace" in err()
 
 
+def test_call_and_query_helpers(monkeypatch):
+    """_lib.call hands a tensor over as its data pointer and None as NULL, and raises the library's own message
+    (host tensors, never dereferenced: each call stops at a check before any launch); _lib.query returns what the
+    direct ctypes call returns and asks the library once per (name, arguments)."""
+    import ctypes
+    import pytest
+    import torch
+    import datou_gomoku_muzero_amd._lib as L
+    lib = L.load()
+    need = ctypes.c_size_t()
+    assert lib.gmz_bn_workspace_bytes(1, 360, 128, 225, ctypes.byref(need)) == 0
+    t = torch.zeros(8)
+
+    def bn_forward(dtype, ws_bytes):
+        L.call("gmz_bn_forward", dtype, 1, t, None, None, 360, 128, 225, t, t, 1e-4, 0.1, None, None, None, 1, t, t, t,
+               ws_bytes, None)
+
+    with pytest.raises(L.GmzError, match="workspace"):
+        bn_forward(1, need.value - 8)
+    with pytest.raises(L.GmzError, match=r"dtype must be 0 \(f32\), 1 \(f16\) or 2 \(bf16\)"):
+        bn_forward(7, need.value)
+    calls = [0]
+    real = lib.gmz_bn_workspace_bytes
+
+    def counted(*a):
+        calls[0] += 1
+        return real(*a)
+
+    monkeypatch.setattr(lib, "gmz_bn_workspace_bytes", counted)
+    monkeypatch.setattr(L, "_QUERIED", {})
+    assert L.query("gmz_bn_workspace_bytes", 1, 360, 128, 225) == need.value and calls[0] == 1
+    assert L.query("gmz_bn_workspace_bytes", 1, 360, 128, 225) == need.value and calls[0] == 1
+    assert L.query("gmz_bn_workspace_bytes", 1, 37, 128, 225) > 0 and calls[0] == 2
+
+
 def test_round6_entry_points_check_before_launching():
     """The round-6 additions keep the same contract: the fused optimiser's workspace and gradient alignment, the
     deferred BatchNorm's statistics partials, the BatchNorm-apply conv's slots and aliasing — all refused before
