@@ -742,6 +742,14 @@ int bn_forward_stats(const void *x, const void *res, int B, int C, int S, const 
   return 0;
 }
 
+// reduction workgroups per segment of bn_forward_seg's own reduction pass: the channels-last splits shared out
+// over the segments, at least one each.  Segments of fewer than 16 pixels ((B / nseg) * S < 16) therefore write
+// nseg slots, MORE than splits_for's B * S / 16, which gmz_bn_forward_seg checks against the workspace it is given.
+static int seg_splits(int B, int nseg, int C, int S) {
+  const int sps = splits_for(B, C, S, 1) / nseg;
+  return sps < 1 ? 1 : sps;
+}
+
 // training-mode forward of nseg equal row segments at once, channels-last: each segment's statistics over its own
 // masked rows (per-board conv partials board_stats [C][B][3] when given, else a reduction pass with the splits
 // grouped by segment), save [nseg][2][C], the running statistics updated segment after segment
@@ -753,8 +761,7 @@ int bn_forward_seg(const void *x, const void *res, const uint8_t *mask, int B, i
   const double *parts = board_stats;
   int sps = B / nseg;
   if (!board_stats) {
-    sps = splits_for(B, C, S, 1) / nseg;
-    if (sps < 1) sps = 1;
+    sps = seg_splits(B, nseg, C, S);
     if (V == 8)
       hipLaunchKernelGGL((k_bnl_red<T, 0, 8>), dim3(nseg * sps), dim3(BN_THREADS), 0, st, (const T *)x, (const T *)nullptr,
                          (const T *)nullptr, mask, B, C, S, (const float *)nullptr, 0, (double *)ws, nseg);
@@ -1173,6 +1180,12 @@ GMZ_EXPORT int gmz_bn_forward_seg(int dtype, const void *x, const void *res, con
   if (check_layout(1, C)) return -1;
   if (!x || !y || !gamma || !beta || !save || !ws) return fail("gmz_bn_forward_seg: null operand");
   if (check_bn_ws("gmz_bn_forward_seg", 1, B, C, S, ws_bytes)) return -1;
+  if (!board_stats) {  // the reduction pass writes nseg * seg_splits slots: more than the workspace's when segments are tiny
+    const size_t need = (size_t)C * nseg * seg_splits(B, nseg, C, S) * 3 * sizeof(double);
+    if (ws_bytes < need)
+      return fail("gmz_bn_forward_seg: workspace of " + std::to_string(ws_bytes) + " bytes, " + std::to_string(nseg) +
+                  " segments of fewer than 16 pixels need " + std::to_string(need) + " (C * nseg * 24)");
+  }
   if (board_stats && check_parts("gmz_bn_forward_seg", C, B, board_stats_bytes)) return -1;
   if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward_seg: running stats pair");
   hipStream_t st = (hipStream_t)stream;

@@ -401,7 +401,10 @@ int gmz_bn_backward_acc_m(int dtype, int layout, const void *x_dev, const void *
  * its own masked rows, save_dev f32 [nseg][2][C] = per segment (mean, invstd), the running statistics updated by
  * the segments in order (= nseg gmz_bn_forward calls).  board_stats_dev: per-board partials from
  * gmz_conv3x3_forward_board_stats (f64 [C][B][3], board_stats_bytes >= C * B * 24) or NULL (a reduction pass).
- * workspace_dev: gmz_bn_workspace_bytes(1, B, C, S).  (ABI 8) */
+ * workspace_dev: gmz_bn_workspace_bytes(1, B, C, S), which is enough whenever a segment has at least 16 pixels
+ * ((B / nseg) * S >= 16, every trainer shape) or board_stats_dev is given.  The reduction pass gives every segment
+ * at least one partial slot, so with smaller segments and board_stats_dev NULL it writes C * nseg * 24 bytes: a
+ * shorter workspace is refused before any launch, with that size in gmz_last_error().  (ABI 8) */
 int gmz_bn_forward_seg(int dtype, const void *x_dev, const void *res_dev, const uint8_t *mask_dev, int B, int nseg,
                        int C, int S, const float *gamma_dev, const float *beta_dev, float eps, float momentum,
                        float *running_mean_dev, float *running_var_dev, int64_t *num_batches_dev, int relu, void *y_dev,

@@ -69,6 +69,16 @@ def test_capacity_arguments_fail_before_any_launch():
     assert lib.gmz_bn_backward_stats(1, fake, fake, fake, None, 360, 128, 225, fake, fake, 1, fake, None, fake, fake,
                                      fake, ns.value, 128 * ns.value * 24, fake, need.value - 8, None, 0) < 0
     assert "workspace" in err()
+    # gmz_bn_forward_seg's own reduction pass gives each segment a partial slot: segments of fewer than 16 pixels
+    # need C * nseg * 24 bytes, more than gmz_bn_workspace_bytes(1, B, C, S), and are refused with that size
+    for (nseg, B, S, C), (have, want) in {(6, 6, 9, 8): (640, 1152), (32, 32, 4, 128): (25600, 98304)}.items():
+        assert lib.gmz_bn_workspace_bytes(1, B, C, S, ctypes.byref(need)) == 0 and need.value == have
+        assert lib.gmz_bn_forward_seg(1, fake, None, None, B, nseg, C, S, fake, fake, 1e-4, 0.1, None, None, None, 1,
+                                      fake, fake, fake, need.value, None, 0, None) < 0
+        assert "workspace" in err() and str(want) in err()
+        assert lib.gmz_bn_forward_seg(1, fake, None, None, B, nseg, C, S, fake, fake, 1e-4, 0.1, None, None, None, 1,
+                                      fake, fake, fake, want - 8, None, 0, None) < 0
+        assert str(want) in err()
     assert lib.gmz_head_conv1x1_workspace_bytes(360 * 225, 3, ctypes.byref(need)) == 0
     assert lib.gmz_head_conv1x1_backward(1, fake, 360 * 225, 128, fake, 2, fake, 1, fake, fake, fake, None, None, None,
                                          None, 0, fake, need.value - 4, None) < 0
