@@ -62,6 +62,9 @@ _SIGS = {
     "gmz_engine_set_simulations": ([P, I], I),
     "gmz_engine_play_refill": ([P, P, P, P, P, P, P, I, P, I, P, P, P, P, I, P, P, P, I, I, P, P], I),
     "gmz_replay_ingest": ([I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, P, SZ, P, P, P], I),
+    "gmz_replay_gather": ([I, I, I, I, I, P, P, P, P, P, P, P, I, I, P, SZ, P, SZ, P, SZ, P, SZ, P, SZ, P, SZ, P, SZ, P], I),
+    "gmz_replay_per_sample_workspace_bytes": ([I, I, ctypes.POINTER(SZ)], I),
+    "gmz_replay_per_sample": ([P, P, I, I, P, SZ, P, SZ, P, SZ, P], I),
     "gmz_gumbel_keyed":([P, P, U64, I, I, P, SZ, P], I),
     "gmz_hashnet_initial": ([P, I, I, P, P, P, P, P], I),
     "gmz_hashnet_recurrent": ([P, P, P, P, I, I, P, P, P, P], I),

@@ -1,5 +1,6 @@
 // gmz_replay.hip — finished self-play games from the device history (worker.GameHistory) straight into the trainer's
-// device replay ring (trainer.ReplayBuffer), one launch per self-play move.
+// device replay ring (trainer.ReplayBuffer), one launch per self-play move; and, further down, training batches from
+// that ring into the trainer's inputs (gmz_replay_gather) and the PER draw that picks them (gmz_replay_per_sample).
 //
 // Bit-exact restatement of records.final_rewards + records.compute_n_step_returns + loop.slices_from_game (built
 // with -ffp-contract=off): the ring holds what the host path would have uploaded, bit for bit.
@@ -111,6 +112,213 @@ __global__ __launch_bounds__(256) void k_replay_ingest(const ReplayArgs a, const
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Training batches from the ring into the trainer's static inputs (trainer.ReplayBuffer.gather_into), one launch.
+//
+// Bit-exact restatement of trainer.augment on batch = (obs[idx].float(), act[idx], rew[idx], pol[idx], val[idx]):
+//   planes, policies  torch.rot90(x, k) then torch.flip of the last axis when flip.  Destination cell (i, j) reads the
+//                     source cell through the inverse map: jj = flip ? H-1-j : j, then
+//                     k = 0: (i, jj)   k = 1: (jj, H-1-i)   k = 2: (H-1-i, H-1-jj)   k = 3: (H-1-jj, i);
+//                     u8 0/1 planes widen to f32 exactly.
+//   augmented action  augment's own formulae on r = a // H, c = a % H (floor division, python's modulus):
+//                     k = 1: r, c = c, H-1-r   k = 2: r, c = H-1-r, H-1-c   k = 3: r, c = H-1-c, r;
+//                     flip: c = H-1-c; out = r * H + c.  The plain action output is a itself (-1 stays -1); for
+//                     a = -1 the augmented output is what these formulae give (-1 under the identity), as augment's
+//                     is: the loss masks those entries by the plain action.
+// One workgroup per (sample, unroll step); writes run along the destination.  A row whose index lies outside
+// 0..count-1 writes nothing.
+struct GatherArgs {
+  const uint8_t *r_obs;
+  const int32_t *r_act;
+  const float *r_rew;
+  const float *r_pol;
+  const float *r_val;
+  const int64_t *idx;
+  const float *w;
+  float *o_obs;
+  int64_t *o_act;
+  float *o_rew;
+  float *o_pol;
+  float *o_val;
+  int64_t *o_aug;
+  float *o_w;
+  int H, A, U, count, k, flip;
+};
+
+__device__ __forceinline__ int gather_src_cell(int d, int H, int k, int flip) {
+  const int i = d / H, j = d - i * H, jj = flip ? H - 1 - j : j;
+  int si, sj;
+  if (k == 0) { si = i; sj = jj; }
+  else if (k == 1) { si = jj; sj = H - 1 - i; }
+  else if (k == 2) { si = H - 1 - i; sj = H - 1 - jj; }
+  else { si = H - 1 - jj; sj = i; }
+  return si * H + sj;
+}
+
+__device__ __forceinline__ int64_t gather_aug_action(int a, int H, int k, int flip) {
+  int r = a / H;
+  if (a < 0 && r * H != a) --r;  // floor division
+  int c = a - r * H;             // python's modulus: 0..H-1
+  int rr = r, cc = c;
+  if (k == 1) { rr = c; cc = H - 1 - r; }
+  else if (k == 2) { rr = H - 1 - r; cc = H - 1 - c; }
+  else if (k == 3) { rr = H - 1 - c; cc = r; }
+  if (flip) cc = H - 1 - cc;
+  return (int64_t)rr * H + cc;
+}
+
+__global__ __launch_bounds__(256) void k_replay_gather(const GatherArgs a) {
+  const int U1 = a.U + 1;
+  const int b = (int)blockIdx.x / U1, u = (int)blockIdx.x - b * U1;
+  const int64_t s = a.idx[b];
+  if (s < 0 || s >= (int64_t)a.count) return;  // a row the host did not vouch for
+  const int A = a.A, H = a.H, U = a.U, tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  if (tid == 0) {
+    a.o_val[(size_t)b * U1 + u] = a.r_val[(size_t)s * U1 + u];
+    if (u < U) {
+      const int act = a.r_act[(size_t)s * U + u];
+      a.o_act[(size_t)b * U + u] = (int64_t)act;
+      a.o_aug[(size_t)b * U + u] = gather_aug_action(act, H, a.k, a.flip);
+      a.o_rew[(size_t)b * U + u] = a.r_rew[(size_t)s * U + u];
+    }
+    if (u == 0) a.o_w[b] = a.w ? a.w[b] : 1.0f;
+  }
+  const uint8_t *so = a.r_obs + ((size_t)s * U1 + u) * 3 * A;
+  const float *sp = a.r_pol + ((size_t)s * U1 + u) * A;
+  float *dobs = a.o_obs + ((size_t)b * U1 + u) * 3 * A;
+  float *dpol = a.o_pol + ((size_t)b * U1 + u) * A;
+  for (int d = tid; d < A; d += nt) {
+    const int src = gather_src_cell(d, H, a.k, a.flip);
+    dobs[d] = (float)so[src];
+    dobs[A + d] = (float)so[A + src];
+    dobs[2 * A + d] = (float)so[2 * A + src];
+    dpol[d] = sp[src];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The stratified proportional draw of ReplayBuffer.sample's PER branch, three launches, everything in f64.
+//
+// Summation order (fixed; p[j] = (double)prio[j] for j < count, 0.0 past count; "+" is one rounded f64 addition and
+// every sum below runs left to right, starting from its first term):
+//   group   g holds elements 16g .. 16g+15:          w[g][e] = p[16g] + p[16g+1] + ... + p[16g+e],   l[g] = w[g][15]
+//   chunk   c holds groups 64c .. 64c+63:            S[c]    = l[64c] + l[64c+1] + ... + l[64c+63]
+//   chunks  T[c] = S[0] + S[1] + ... + S[c]          (T[-1] = 0.0);   total = T[nchunks-1]
+//   bases   b[c][0] = T[c-1],  b[c][t+1] = b[c][t] + l[64c+t]
+//   cum[j]  = min(b[c][t] + w[64c+t][e], T[c])       for j = 1024c + 16t + e,
+//             except cum[j] = T[c] for the last j < count of chunk c.
+// Every term is >= 0, so each running sum is non-decreasing and cum is non-decreasing in j, with cum[count-1] = total.
+//   u_i    = ((double)i + r_i) * (total / (double)B)
+//   idx_i  = min(first j with cum[j] >= u_i, count-1)       prob_i = p[idx_i] / total
+// Launch 1: one wave per chunk writes l and S.  Launch 2: one wave turns S into T in place.  Launch 3: one wave per
+// draw: a binary search over T, the chunk's 64 bases by a 64-step running sum over lane values, a ballot, the group's
+// 16 elements likewise.  Nothing depends on the grid: a wave's work is fixed by its chunk or its draw.
+constexpr int PER_GROUP = 16, PER_GROUPS = 64, PER_CHUNK = PER_GROUP * PER_GROUPS;
+
+__device__ __forceinline__ double bcast_d(double v, int lane) {
+  return __hiloint2double(__shfl(__double2hiint(v), lane, 64), __shfl(__double2loint(v), lane, 64));
+}
+
+// running left-to-right sum over the wave's lane values from `start`: before = start + v[0] + ... + v[lane-1],
+// returns the sum over all 64 lanes (wave-uniform)
+__device__ __forceinline__ double wave_running_sum(double start, double v, int lane, double &before) {
+  double acc = start;
+  before = start;
+#pragma unroll
+  for (int t = 0; t < 64; ++t) {
+    if (lane == t) before = acc;
+    acc = acc + bcast_d(v, t);
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void k_per_groups(const float *prio, int count, int nchunks, double *l, double *S) {
+  const int lane = (int)threadIdx.x & 63;
+  const int c = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (c >= nchunks) return;  // whole waves only
+  const long g = (long)c * PER_GROUPS + lane;
+  const long j0 = g * PER_GROUP;
+  double s = 0.0;
+  if (j0 < count) {
+    s = (double)prio[j0];
+    for (int e = 1; e < PER_GROUP; ++e)
+      if (j0 + e < count) s = s + (double)prio[j0 + e];
+    l[g] = s;
+  }
+  // S[c] = l[64c] + ... (groups past count are 0.0: x + 0.0 == x)
+  double acc = bcast_d(s, 0);
+#pragma unroll
+  for (int t = 1; t < 64; ++t) acc = acc + bcast_d(s, t);
+  if (lane == 0) S[c] = acc;
+}
+
+__global__ __launch_bounds__(64) void k_per_chunks(double *S, int nchunks) {
+  const int lane = (int)threadIdx.x;
+  double carry = 0.0;
+  for (int c0 = 0; c0 < nchunks; c0 += 64) {
+    const int c = c0 + lane;
+    const double s = c < nchunks ? S[c] : 0.0;
+    double before;
+    carry = wave_running_sum(carry, s, lane, before);
+    if (c < nchunks) S[c] = before + s;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_per_draw(const float *prio, const double *r, int count, int B, int nchunks,
+                                                  const double *l, const double *T, int64_t *idx, double *prob) {
+  const int lane = (int)threadIdx.x & 63;
+  const int i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (i >= B) return;  // whole waves only
+  const double total = T[nchunks - 1];
+  const double u = ((double)i + r[i]) * (total / (double)B);
+  // first chunk with T[c] >= u
+  int lo = 0, hi = nchunks;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (T[mid] >= u) hi = mid; else lo = mid + 1;
+  }
+  long j = (long)count - 1;  // the clamp: u beyond the total
+  if (lo < nchunks) {
+    const int c = lo;
+    const long ngroups = ((long)count + PER_GROUP - 1) / PER_GROUP;
+    const long g = (long)c * PER_GROUPS + lane;
+    const double lg = g < ngroups ? l[g] : 0.0;
+    double base;
+    wave_running_sum(c > 0 ? T[c - 1] : 0.0, lg, lane, base);
+    const unsigned long long m = __ballot(g < ngroups && base + lg >= u);
+    const long last = ((long)(c + 1) * PER_CHUNK < count ? (long)(c + 1) * PER_CHUNK : (long)count) - 1;
+    j = last;  // cum[last j of the chunk] = T[c] >= u
+    if (m) {
+      const int t = __ffsll((long long)m) - 1;
+      const double bt = bcast_d(base, t);
+      const long e0 = ((long)c * PER_GROUPS + t) * PER_GROUP;
+      const long je = e0 + (lane & (PER_GROUP - 1));
+      const double pe = (lane < PER_GROUP && je < count) ? (double)prio[je] : 0.0;
+      double acc = bcast_d(pe, 0), w = acc;
+#pragma unroll
+      for (int e = 1; e < PER_GROUP; ++e) {
+        acc = acc + bcast_d(pe, e);
+        if (lane == e) w = acc;
+      }
+      const unsigned long long m2 = __ballot(lane < PER_GROUP && je < count && bt + w >= u);
+      if (m2) {
+        const long jf = e0 + (__ffsll((long long)m2) - 1);
+        if (jf < j) j = jf;
+      }
+    }
+  }
+  if (lane == 0) {
+    idx[i] = (int64_t)j;
+    prob[i] = (double)prio[j] / total;
+  }
+}
+
+static inline void per_sizes(int count, long &ngroups, long &nchunks) {
+  ngroups = ((long)count + PER_GROUP - 1) / PER_GROUP;
+  nchunks = ((long)count + PER_CHUNK - 1) / PER_CHUNK;
+}
+
 }  // namespace gmz
 
 using namespace gmz;
@@ -178,6 +386,101 @@ GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G,
   ReplayPow P;
   for (int i = 0; i <= GMZ_REPLAY_MAX_N_STEPS; ++i) P.pw[i] = i <= n_steps ? discount_pow[i] : 0.0;
   hipLaunchKernelGGL(k_replay_ingest, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a, P);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_replay_gather(int board_size, int unroll, int N, int count, int B, const uint8_t *ring_obs_dev,
+                                 const int32_t *ring_act_dev, const float *ring_rew_dev, const float *ring_pol_dev,
+                                 const float *ring_val_dev, const int64_t *idx_dev, const float *w_dev, int k, int flip,
+                                 float *obs_out_dev, size_t obs_out_bytes, int64_t *act_out_dev, size_t act_out_bytes,
+                                 float *rew_out_dev, size_t rew_out_bytes, float *pol_out_dev, size_t pol_out_bytes,
+                                 float *val_out_dev, size_t val_out_bytes, int64_t *act_aug_out_dev,
+                                 size_t act_aug_out_bytes, float *w_out_dev, size_t w_out_bytes, void *stream) {
+  if (board_size < 5 || board_size > 22)
+    return fail("gmz_replay_gather: board_size " + std::to_string(board_size) + " outside 5..22");
+  if (unroll < 1) return fail("gmz_replay_gather: unroll " + std::to_string(unroll) + " < 1");
+  if (B < 1) return fail("gmz_replay_gather: B " + std::to_string(B) + " < 1");
+  if (N < 1) return fail("gmz_replay_gather: N " + std::to_string(N) + " < 1");
+  if (count < 1 || count > N)
+    return fail("gmz_replay_gather: count " + std::to_string(count) + " outside 1..N = " + std::to_string(N));
+  if (k < 0 || k > 3) return fail("gmz_replay_gather: k " + std::to_string(k) + " outside 0..3");
+  if (flip != 0 && flip != 1) return fail("gmz_replay_gather: flip " + std::to_string(flip) + " is neither 0 nor 1");
+  if (!ring_obs_dev || !ring_act_dev || !ring_rew_dev || !ring_pol_dev || !ring_val_dev)
+    return fail("gmz_replay_gather: a ring pointer is NULL");
+  if (!idx_dev) return fail("gmz_replay_gather: idx_dev is NULL");
+  if (!obs_out_dev || !act_out_dev || !rew_out_dev || !pol_out_dev || !val_out_dev || !act_aug_out_dev || !w_out_dev)
+    return fail("gmz_replay_gather: an output pointer is NULL");
+  const size_t A = (size_t)board_size * board_size, U = (size_t)unroll, nb = (size_t)B;
+  if ((nb * (U + 1) > (size_t)0x7fffffff))
+    return fail("gmz_replay_gather: B * (unroll + 1) = " + std::to_string(nb * (U + 1)) + " passes one launch's grid");
+  const struct { const char *name; size_t have, need; } caps[] = {
+      {"obs_out", obs_out_bytes, nb * (U + 1) * 3 * A * sizeof(float)},
+      {"act_out", act_out_bytes, nb * U * sizeof(int64_t)},
+      {"rew_out", rew_out_bytes, nb * U * sizeof(float)},
+      {"pol_out", pol_out_bytes, nb * (U + 1) * A * sizeof(float)},
+      {"val_out", val_out_bytes, nb * (U + 1) * sizeof(float)},
+      {"act_aug_out", act_aug_out_bytes, nb * U * sizeof(int64_t)},
+      {"w_out", w_out_bytes, nb * sizeof(float)},
+  };
+  for (const auto &c : caps)
+    if (c.have < c.need)
+      return fail(std::string("gmz_replay_gather: ") + c.name + " of " + std::to_string(c.have) +
+                  " bytes is short of " + std::to_string(c.need));
+  GatherArgs a;
+  a.r_obs = ring_obs_dev; a.r_act = ring_act_dev; a.r_rew = ring_rew_dev; a.r_pol = ring_pol_dev; a.r_val = ring_val_dev;
+  a.idx = idx_dev; a.w = w_dev;
+  a.o_obs = obs_out_dev; a.o_act = act_out_dev; a.o_rew = rew_out_dev; a.o_pol = pol_out_dev; a.o_val = val_out_dev;
+  a.o_aug = act_aug_out_dev; a.o_w = w_out_dev;
+  a.H = board_size; a.A = (int)A; a.U = unroll; a.count = count; a.k = k; a.flip = flip;
+  hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)(nb * (U + 1))), dim3(256), 0, (hipStream_t)stream, a);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_replay_per_sample_workspace_bytes(int count, int B, size_t *out) {
+  if (count < 1) return fail("gmz_replay_per_sample_workspace_bytes: count " + std::to_string(count) + " < 1");
+  if (B < 1) return fail("gmz_replay_per_sample_workspace_bytes: B " + std::to_string(B) + " < 1");
+  if (!out) return fail("gmz_replay_per_sample_workspace_bytes: out is NULL");
+  long ngroups, nchunks;
+  per_sizes(count, ngroups, nchunks);
+  *out = (size_t)(ngroups + nchunks) * sizeof(double);
+  return 0;
+}
+
+GMZ_EXPORT int gmz_replay_per_sample(const float *prio_dev, const double *r_dev, int count, int B, int64_t *idx_dev,
+                                     size_t idx_bytes, double *prob_dev, size_t prob_bytes, void *workspace_dev,
+                                     size_t ws_bytes, void *stream) {
+  if (count < 1) return fail("gmz_replay_per_sample: count " + std::to_string(count) + " < 1");
+  if (B < 1) return fail("gmz_replay_per_sample: B " + std::to_string(B) + " < 1");
+  if (!prio_dev) return fail("gmz_replay_per_sample: prio_dev is NULL");
+  if (!r_dev) return fail("gmz_replay_per_sample: r_dev is NULL");
+  if (!idx_dev) return fail("gmz_replay_per_sample: idx_dev is NULL");
+  if (!prob_dev) return fail("gmz_replay_per_sample: prob_dev is NULL");
+  if (!workspace_dev) return fail("gmz_replay_per_sample: workspace_dev is NULL");
+  if ((uintptr_t)workspace_dev % sizeof(double))
+    return fail("gmz_replay_per_sample: workspace_dev is not 8-byte aligned");
+  long ngroups, nchunks;
+  per_sizes(count, ngroups, nchunks);
+  const size_t need = (size_t)(ngroups + nchunks) * sizeof(double);
+  if (ws_bytes < need)
+    return fail("gmz_replay_per_sample: workspace of " + std::to_string(ws_bytes) + " bytes is short of " +
+                std::to_string(need) + " (gmz_replay_per_sample_workspace_bytes)");
+  if (idx_bytes < (size_t)B * sizeof(int64_t))
+    return fail("gmz_replay_per_sample: idx of " + std::to_string(idx_bytes) + " bytes is short of " +
+                std::to_string((size_t)B * sizeof(int64_t)));
+  if (prob_bytes < (size_t)B * sizeof(double))
+    return fail("gmz_replay_per_sample: prob of " + std::to_string(prob_bytes) + " bytes is short of " +
+                std::to_string((size_t)B * sizeof(double)));
+  double *l = (double *)workspace_dev, *T = l + ngroups;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_per_groups, dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, st, prio_dev, count, (int)nchunks,
+                     l, T);
+  GMZ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_per_chunks, dim3(1), dim3(64), 0, st, T, (int)nchunks);
+  GMZ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_per_draw, dim3((unsigned)(((long)B + 3) / 4)), dim3(256), 0, st, prio_dev, r_dev, count, B,
+                     (int)nchunks, (const double *)l, (const double *)T, idx_dev, prob_dev);
   GMZ_LAUNCH_CHECK();
   return 0;
 }

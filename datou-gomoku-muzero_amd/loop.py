@@ -14,6 +14,8 @@ own share of the work, time-sliced on its GPU:
               replay shard (trainer.ReplayBuffer) — no data crosses ranks; ``device_ingest=True``: the
               slices go from the device history into the shard by one HIP launch per move
               (gmz_replay_ingest, bit-identical; nothing but a job table crosses the bus);
+              ``device_batches=True``: a training batch goes from the shard into the trainer's inputs by the
+              PER draw and one gather launch in HIP (gmz_replay_per_sample, gmz_replay_gather; Trainer.step_from);
   training    data-parallel: each rank samples its batch from its own shard; gradients are averaged
               by one flat-bucket all-reduce per step (RCCL over xGMI); PER (sharded):
               IS weights from the global slice count (all-reduce SUM) normalised by the global batch
@@ -129,7 +131,7 @@ class C4Loop:
 
     def __init__(self, selfplay, trainer, buffer, cfg, batch_size, dist=None, moves_per_iter=1,
                  train_steps_per_iter=1, model_update_interval=1000, seed=0, device="cuda", concurrent=False,
-                 device_ingest=False):
+                 device_ingest=False, device_batches=False):
         self.sp, self.tr, self.rb, self.cfg = selfplay, trainer, buffer, cfg
         self.B, self.dist = int(batch_size), dist
         self.moves_per_iter, self.train_steps_per_iter = int(moves_per_iter), int(train_steps_per_iter)
@@ -160,6 +162,17 @@ class C4Loop:
                     getattr(buffer.cfg, k) for k in ("BOARD_SIZE", "NUM_UNROLL_STEPS", "N_STEPS", "DISCOUNT")):
                 raise ValueError("device_ingest: the loop's config and the buffer's disagree on the slices' geometry")
             selfplay.ingest_into(buffer, self.train_stream)
+        # device_batches: a training batch goes from the shard to the trainer's inputs in HIP (the PER draw and one
+        # gather launch, Trainer.step_from); off = ReplayBuffer.sample's torch indexing and Trainer.step's copies
+        self.device_batches = bool(device_batches)
+        if self.device_batches:
+            if self.device.type != "cuda":
+                raise ValueError("device_batches needs the loop on a GPU")
+            if buffer.obs.device.type != "cuda":
+                raise ValueError("device_batches needs a device-resident ReplayBuffer, not one on %s" % buffer.obs.device)
+            if not hasattr(trainer, "step_from") or int(trainer.cfg.PHYSICAL_BATCH_SIZE) != self.B:
+                raise ValueError("device_batches: the trainer steps on its PHYSICAL_BATCH_SIZE, not on a batch of %d"
+                                 % self.B)
 
     # ---------------------------------------------------------------- pieces
     def _add_games(self, done):
@@ -208,8 +221,11 @@ class C4Loop:
         self.weight_pushes += 1
 
     def train_step(self):
-        batch, idx, w = self.rb.sample(self.B, self.rs, dist=self.dist)
-        logs, td = self.tr.step(batch, w, sync=False)
+        if self.device_batches:
+            logs, td, idx = self.tr.step_from(self.rb, self.rs, dist=self.dist, sync=False)
+        else:
+            batch, idx, w = self.rb.sample(self.B, self.rs, dist=self.dist)
+            logs, td = self.tr.step(batch, w, sync=False)
         self.rb.update_priorities(idx, td, dist=self.dist)
         self.last_logs = logs
         self.train_steps += 1
@@ -282,7 +298,8 @@ def run_c4(args, rank, world, dist, backend, log=print):
                   moves_per_iter=args.loop_moves_per_iter, train_steps_per_iter=args.loop_train_per_iter,
                   model_update_interval=args.loop_update_interval, seed=args.seed,
                   concurrent=getattr(args, "loop_concurrent", False),
-                  device_ingest=getattr(args, "loop_device_ingest", False))
+                  device_ingest=getattr(args, "loop_device_ingest", False),
+                  device_batches=getattr(args, "loop_device_batches", False))
     t_w = time.perf_counter()
     loop.run(args.loop_warmup)
     torch.cuda.synchronize()

@@ -2056,6 +2056,7 @@ class ReplayBuffer:
         self.val = torch.zeros(self.N, U + 1, dtype=torch.float32, device=d)
         self.prio = torch.zeros(self.N, dtype=torch.float32, device=d)
         self.ptr, self.count, self.max_priority, self.device = 0, 0, 1.0, d
+        self._per_ws = None  # gmz_replay_per_sample's workspace (sample_indices(hip=True)), built at first use
 
     def __len__(self):
         return self.count
@@ -2167,6 +2168,87 @@ class ReplayBuffer:
             w = torch.ones(B, device=self.device)
         batch = (self.obs[idx].float(), self.act[idx], self.rew[idx], self.pol[idx], self.val[idx])
         return batch, idx, w
+
+    def sample_indices(self, B, rng=np.random, dist=None, hip=False):
+        """The index and weight half of :meth:`sample` -> (idx int64 [B], w f32 [B]), or None when the ring holds
+        fewer than B slices.  It consumes ``rng`` exactly as ``sample`` does.  ``hip``: with PER on, the draw
+        (priorities' prefix sums, the search, the probabilities) is gmz_replay_per_sample on the current stream,
+        in the summation order include/gmz.h states; the IS weights and the sharded-PER all-reduces stay the lines
+        of ``sample``, fed with its probabilities.  With PER off both settings draw the same host permutation."""
+        if hip and self.obs.device.type != "cuda":
+            raise ValueError("sample_indices(hip=True) needs a device-resident ReplayBuffer, not one on %s"
+                             % self.obs.device)
+        if self.count < B:
+            return None
+        if not self.cfg.ENABLE_PER:
+            idx = torch.from_numpy(rng.choice(self.count, B, replace=False)).to(self.device)
+            return idx, torch.ones(B, device=self.device)
+        r = torch.from_numpy(rng.random_sample(B)).to(self.device, non_blocking=True)
+        if hip:
+            from . import _lib as _L
+            ws = self._per_ws
+            if ws is None:  # sized for a full ring: the need grows with count
+                need = _L.query("gmz_replay_per_sample_workspace_bytes", int(self.N), int(B))
+                ws = self._per_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+            idx = torch.empty(B, dtype=torch.int64, device=self.device)
+            prob = torch.empty(B, dtype=torch.float64, device=self.device)
+            _L.call("gmz_replay_per_sample", self.prio, r, int(self.count), int(B), idx, _L.nbytes(idx), prob,
+                    _L.nbytes(prob), ws, _L.nbytes(ws), _L.stream_ptr())
+        else:
+            p = self.prio[: self.count].double()
+            cum = torch.cumsum(p, 0)
+            total = cum[-1]
+            u = (torch.arange(B, device=self.device, dtype=torch.float64) + r) * (total / B)
+            idx = torch.searchsorted(cum, u).clamp_max(self.count - 1)
+            prob = p[idx] / total
+        count = float(self.count)
+        if dist is not None and dist.get_world_size() > 1:
+            count = _allreduce(torch.tensor([count], dtype=torch.float64, device=self.device), dist)
+            prob = prob / dist.get_world_size()
+        w = (count * prob) ** (-self.cfg.PER_BETA)
+        wmax = w.max()
+        if dist is not None and dist.get_world_size() > 1:
+            wmax = _allreduce(wmax.reshape(1), dist, max_op=True)[0]
+        return idx, (w / wmax).float()
+
+    def gather_into(self, dst, idx, w, k, flip):
+        """The batch of ring slots ``idx`` (int64 [B], repeats allowed) under the board symmetry (k quarter turns,
+        then the mirror when ``flip``) written into ``dst``, a 7-tuple shaped like Trainer._static (observations f32
+        [B, U+1, 3, H, H], actions int64 [B, U], rewards, policies [B, U+1, A], search values, augmented actions
+        int64, weights f32 [B]; ``w`` None = ones): one HIP launch (gmz_replay_gather) on the current stream,
+        bit-identical to Trainer._augment_into_static on the batch :meth:`sample` builds by torch indexing."""
+        from . import _lib as _L
+        c = self.cfg
+        U, H = int(c.NUM_UNROLL_STEPS), int(c.BOARD_SIZE)
+        A, dev = H * H, self.obs.device
+        if dev.type != "cuda":
+            raise ValueError("gather_into needs a device-resident ReplayBuffer, not one on %s" % dev)
+        if tuple(self.obs.shape[1:]) != (U + 1, 3, H, H):
+            raise ValueError("ring planes %s do not hold %d unroll steps of %dx%d boards" % (tuple(self.obs.shape), U, H, H))
+        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev \
+                or not idx.is_contiguous():
+            raise ValueError("idx must be a contiguous int64 vector on %s" % dev)
+        B = int(idx.shape[0])
+        if w is not None and (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (B,)
+                              or w.device != dev or not w.is_contiguous()):
+            raise ValueError("w must be None or a contiguous float32 vector of %d weights on %s" % (B, dev))
+        f32, i64 = torch.float32, torch.int64
+        want = (("observations", f32, (B, U + 1, 3, H, H)), ("actions", i64, (B, U)), ("rewards", f32, (B, U)),
+                ("policies", f32, (B, U + 1, A)), ("values", f32, (B, U + 1)), ("augmented actions", i64, (B, U)),
+                ("weights", f32, (B,)))
+        if len(dst) != len(want):
+            raise ValueError("dst holds %d tensors, not the trainer's %d static inputs" % (len(dst), len(want)))
+        for t, (name, dt, shape) in zip(dst, want):
+            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or t.device != dev \
+                    or not t.is_contiguous():
+                raise ValueError("dst %s: expected a contiguous %s tensor of shape %s on %s, got %s %s on %s" % (
+                    name, dt, shape, dev, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
+                    getattr(t, "device", None)))
+        if int(k) not in (0, 1, 2, 3):
+            raise ValueError("k = %r is not a number of quarter turns 0..3" % (k,))
+        sized = [x for t in dst for x in (t, _L.nbytes(t))]
+        _L.call("gmz_replay_gather", H, U, int(self.N), int(self.count), B, self.obs, self.act, self.rew, self.pol,
+                self.val, idx, w, int(k), int(bool(flip)), *sized, _L.stream_ptr())
 
     def update_priorities(self, idx, td, dist=None):
         """replay_buffer.py:96-101; with ``dist`` the running max priority (the priority of newly added
@@ -2546,40 +2628,82 @@ class Trainer:
         """One training step -> ((total, policy, value, reward, consistency) floats, td errors [B]).
         ``sync=False``: the five losses stay a device tensor [5] (no host synchronisation, so the host
         can prepare the next step while this one runs; read them with ``.tolist()`` later)."""
-        c = self.cfg
-        acc = max(1, c.GRADIENT_ACCUMULATION_STEPS)
         if self.graph and self.step_count >= self.graph_warmup:
             self._augment_into_static(batch, is_weights, k, flip)
-            if self._graphs is None:
-                if BATCH_REPACK:  # the job table the captured step will replay, built before the capture
-                    _repack_stale(list(self.model.parameters()) + list(self.target.parameters()), self._pack_tables,
-                                  prepare=True)
-                self._capture()
-            if isinstance(self._graphs, tuple):  # collectives not capturable: the all-reduces between replays
-                g1, gf, g2 = self._graphs
-                g1.replay()
-                work = self._allreduce_start()
-                gf.replay()
-                self._mark_flushed()
-                self._allreduce_finish(work)
-                g2.replay()
-            else:
-                self._graphs.replay()
-            logs, td = self._out
-            td = td.clone()
-            self.sched.step()
+            logs, td = self._graph_step()
         else:
-            last = (self.step_count + 1) % acc == 0
-            overlap = self.dist is not None and last
-            logs, td = self._forward_backward(batch, is_weights, acc, k=k, flip=flip, flush=not overlap)
-            if overlap:  # bucket A's all-reduce beside bucket B's weight gradients
-                work = self._allreduce_start()
-                self._flush()
-                self._mark_flushed()
-                self._allreduce_finish(work)
-            if last:
-                self._update()
-                self.sched.step()
+            logs, td = self._eager_step(batch, is_weights, k, flip)
+        return self._finish_step(logs, td, sync)
+
+    def step_from(self, rb, rng, dist=None, k=None, flip=None, sync=True):
+        """One training step on a batch taken from the device ring ``rb`` without leaving HIP -> (logs, td, idx)
+        as :meth:`step` returns them plus the ring slots drawn (for ``rb.update_priorities(idx, td)``), or None
+        when the shard holds no batch.  The draw is ``rb.sample_indices(PHYSICAL_BATCH_SIZE, rng, dist, hip=True)``;
+        ``k``/``flip`` default to draws from numpy's global RandomState in ``_augment_into_static``'s order; one
+        launch (``rb.gather_into``) writes the augmented batch into the captured step's static inputs, which then
+        runs as in :meth:`step` — a graph replay, or the eager step on those inputs (warm-up, gradient
+        accumulation, ``graph=False``).  ``step`` and ``step_from`` can be mixed on one trainer."""
+        c = self.cfg
+        got = rb.sample_indices(int(c.PHYSICAL_BATCH_SIZE), rng, dist=dist, hip=True)
+        if got is None:
+            return None
+        idx, w = got
+        if k is None:
+            k = np.random.randint(4)
+        if flip is None:
+            flip = bool(np.random.choice([True, False]))
+        if self._static is None:  # _augment_into_static's shapes and dtypes
+            B, U, H = int(c.PHYSICAL_BATCH_SIZE), int(c.NUM_UNROLL_STEPS), int(c.BOARD_SIZE)
+            f32, i64 = torch.float32, torch.int64
+            self._static = tuple(torch.empty(shape, dtype=dt, device=self.device) for dt, shape in (
+                (f32, (B, U + 1, 3, H, H)), (i64, (B, U)), (f32, (B, U)), (f32, (B, U + 1, H * H)), (f32, (B, U + 1)),
+                (i64, (B, U)), (f32, (B,))))
+        rb.gather_into(self._static, idx, w, k, flip)
+        if self.graph and self.step_count >= self.graph_warmup:
+            logs, td = self._graph_step()
+        else:
+            logs, td = self._eager_step(self._static[:6], self._static[6], None, None, augmented=True)
+        return self._finish_step(logs, td, sync) + (idx,)
+
+    def _graph_step(self):
+        """The captured step on what ``_static`` holds, capturing first when due."""
+        if self._graphs is None:
+            if BATCH_REPACK:  # the job table the captured step will replay, built before the capture
+                _repack_stale(list(self.model.parameters()) + list(self.target.parameters()), self._pack_tables,
+                              prepare=True)
+            self._capture()
+        if isinstance(self._graphs, tuple):  # collectives not capturable: the all-reduces between replays
+            g1, gf, g2 = self._graphs
+            g1.replay()
+            work = self._allreduce_start()
+            gf.replay()
+            self._mark_flushed()
+            self._allreduce_finish(work)
+            g2.replay()
+        else:
+            self._graphs.replay()
+        logs, td = self._out
+        td = td.clone()
+        self.sched.step()
+        return logs, td
+
+    def _eager_step(self, batch, is_weights, k, flip, augmented=False):
+        acc = max(1, self.cfg.GRADIENT_ACCUMULATION_STEPS)
+        last = (self.step_count + 1) % acc == 0
+        overlap = self.dist is not None and last
+        logs, td = self._forward_backward(batch, is_weights, acc, k=k, flip=flip, augmented=augmented,
+                                          flush=not overlap)
+        if overlap:  # bucket A's all-reduce beside bucket B's weight gradients
+            work = self._allreduce_start()
+            self._flush()
+            self._mark_flushed()
+            self._allreduce_finish(work)
+        if last:
+            self._update()
+            self.sched.step()
+        return logs, td
+
+    def _finish_step(self, logs, td, sync):
         self.step_count += 1
         if not sync:
             return logs.detach().clone(), td

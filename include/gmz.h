@@ -640,6 +640,48 @@ int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G, int L, con
                       float *ring_prio_dev, int N, const void *jobs_host, int n_jobs, const void *jobs_dev,
                       size_t jobs_dev_bytes, const double *discount_pow, const float *priority_dev, void *stream);
 
+/* ------------------------------------------------------------------ replay batches (ring -> trainer inputs) */
+/* A training batch goes from the ring straight into the trainer's static inputs: one launch on `stream` reads the B
+ * ring slots idx_dev names (int64 [B], repeats allowed), applies one of the eight board symmetries, widens the types
+ * and writes seven contiguous tensors, bit-identical to what Trainer._augment_into_static leaves for
+ * batch = (obs[idx].float(), act[idx], rew[idx], pol[idx], val[idx]) and weights w_dev (f32 [B]; NULL = ones).
+ * Ring as above (obs u8 [N][U+1][3][A], act int32 [N][U], rew f32 [N][U], pol f32 [N][U+1][A], val f32 [N][U+1]), of
+ * which slots 0..count-1 are filled.  Outputs, each with its capacity in bytes: obs f32 [B][U+1][3][H][H], act int64
+ * [B][U] (unchanged; -1 stays -1), rew f32 [B][U], pol f32 [B][U+1][A], val f32 [B][U+1], act_aug int64 [B][U],
+ * w f32 [B].
+ * The symmetry is trainer.augment's: planes and policies follow torch.rot90(., k) and then, when flip, torch.flip of
+ * the last axis; the augmented actions follow augment's own row / column formulae on r = a // H, c = a % H (floor
+ * division), so an action of -1 gives what those formulae give for it (-1 under k = 0, flip = 0), as augment does;
+ * the loss masks such entries by the plain action.
+ * Refused, nothing launched: board_size outside 5..22, unroll < 1, B < 1 (B == 0 is not a valid call), N < 1, count
+ * outside 1..N, k outside 0..3, flip outside {0, 1}, a NULL ring, index or output pointer, an output capacity short
+ * of its size.  On the device a row whose index lies outside 0..count-1 writes nothing (the ingest kernel's rule for
+ * a record the host did not vouch for). */
+int gmz_replay_gather(int board_size, int unroll, int N, int count, int B, const uint8_t *ring_obs_dev,
+                      const int32_t *ring_act_dev, const float *ring_rew_dev, const float *ring_pol_dev,
+                      const float *ring_val_dev, const int64_t *idx_dev, const float *w_dev, int k, int flip,
+                      float *obs_out_dev, size_t obs_out_bytes, int64_t *act_out_dev, size_t act_out_bytes,
+                      float *rew_out_dev, size_t rew_out_bytes, float *pol_out_dev, size_t pol_out_bytes,
+                      float *val_out_dev, size_t val_out_bytes, int64_t *act_aug_out_dev, size_t act_aug_out_bytes,
+                      float *w_out_dev, size_t w_out_bytes, void *stream);
+/* The stratified proportional draw of ReplayBuffer.sample's PER branch: prio_dev f32 [count], r_dev f64 [B] (the
+ * host's uniforms in [0, 1)); idx_dev int64 [B], prob_dev f64 [B], each with its capacity in bytes; workspace_dev of
+ * gmz_replay_per_sample_workspace_bytes(count, B), 8-byte aligned.  Three launches on `stream`, no host
+ * synchronisation.  In f64, with p[j] = (double)prio[j]:
+ *   u_i = ((double)i + r_i) * (total / (double)B);  idx_i = min(first j with cum[j] >= u_i, count - 1)
+ *   (torch.searchsorted's left side and the clamp);  prob_i = p[idx_i] / total.
+ * cum and total are summed in a fixed order, the same bits run to run and independent of the grid (every sum left to
+ * right): groups of 16 elements, w[g][e] = p[16g] + ... + p[16g+e], l[g] = w[g][15]; chunks of 64 groups,
+ * S[c] = l[64c] + ... + l[64c+63]; T[c] = S[0] + ... + S[c], total = T[last]; b[c][0] = T[c-1] (0 for c = 0),
+ * b[c][t+1] = b[c][t] + l[64c+t]; cum[1024c + 16t + e] = min(b[c][t] + w[64c+t][e], T[c]), and cum = T[c] at the
+ * chunk's last element below count.  Elements past count are 0.  cum is non-decreasing for priorities >= 0.
+ * The importance weights are not computed here: (count * prob)^-beta, its max and the sharded-PER all-reduces stay
+ * the caller's.  Refused, nothing launched: count < 1, B < 1, a NULL pointer, a short workspace or output. */
+int gmz_replay_per_sample_workspace_bytes(int count, int B, size_t *out);
+int gmz_replay_per_sample(const float *prio_dev, const double *r_dev, int count, int B, int64_t *idx_dev,
+                          size_t idx_bytes, double *prob_dev, size_t prob_bytes, void *workspace_dev, size_t ws_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
