@@ -1,6 +1,8 @@
 // gmz_replay.hip — finished self-play games from the device history (worker.GameHistory) straight into the trainer's
 // device replay ring (trainer.ReplayBuffer), one launch per self-play move; and, further down, training batches from
 // that ring into the trainer's inputs (gmz_replay_gather) and the PER draw that picks them (gmz_replay_per_sample).
+// Between the two: the ring's own games as engine positions and their re-searched targets back into the ring
+// (gmz_replay_positions, gmz_replay_rewrite).
 //
 // Bit-exact restatement of records.final_rewards + records.compute_n_step_returns + loop.slices_from_game (built
 // with -ffp-contract=off): the ring holds what the host path would have uploaded, bit for bit.
@@ -54,6 +56,17 @@ __device__ __forceinline__ float final_reward(int n, int winner, int t) {
   return (d == 0 || d == 3) ? 1.0f : -1.0f;
 }
 
+// The n-step value target of position t of a game of n moves (the header's "value targets", in that operation
+// order); val[row0 + i] is the search value of position i.  Shared by k_replay_ingest and k_replay_rewrite.
+__device__ __forceinline__ float n_step_target(const ReplayPow &P, int n_steps, int n, int winner, int t,
+                                               const float *val, long row0) {
+  double s = 0.0;
+  for (int i = 0; i < n_steps && t + i < n; ++i) s = s + P.pw[i] * (double)final_reward(n, winner, t + i);
+  float v = (float)s;
+  if (t + n_steps < n) v = v + val[row0 + t + n_steps] * (float)P.pw[n_steps];
+  return v;
+}
+
 __global__ __launch_bounds__(256) void k_replay_ingest(const ReplayArgs a, const ReplayPow P) {
   const int b = (int)blockIdx.x;
   // last job whose first kept slice is <= b
@@ -76,14 +89,7 @@ __global__ __launch_bounds__(256) void k_replay_ingest(const ReplayArgs a, const
 
   for (int u = tid; u <= U; u += nt) {
     const int t = t0 + u;
-    float v = 0.0f;
-    if (t < n) {
-      double s = 0.0;
-      for (int i = 0; i < a.n_steps && t + i < n; ++i) s = s + P.pw[i] * (double)final_reward(n, j.winner, t + i);
-      v = (float)s;
-      if (t + a.n_steps < n) v = v + a.val[hrow + t + a.n_steps] * (float)P.pw[a.n_steps];
-    }
-    a.r_val[ring * (U + 1) + u] = v;
+    a.r_val[ring * (U + 1) + u] = t < n ? n_step_target(P, a.n_steps, n, j.winner, t, a.val, (long)hrow) : 0.0f;
     if (u < U) {
       a.r_rew[ring * U + u] = final_reward(n, j.winner, t);
       a.r_act[ring * U + u] = t < n ? a.act[hrow + t] : -1;
@@ -109,6 +115,101 @@ __global__ __launch_bounds__(256) void k_replay_ingest(const ReplayArgs a, const
     o[A] = opp;
     o[2 * A] = lastp;
     pol[idx] = p;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Re-analysis of games that are already in the ring (reanalysis.RingReanalyser): ring slices become engine positions
+// (gmz_replay_positions), and a search's new policies and values become ring targets (gmz_replay_rewrite).  Both are
+// one pass of memory movement; the rewrite's value targets are n_step_target above, ingest's own.
+//   positions   row r < P reads planes obs[slot, 0] of table row (slot, m): player = +1 for even m, else -1 (the
+//               convention of every opening generator: black moves on even counts); cell = player where the own
+//               plane is set, -player where the opponent plane is set, else 0; last = the set cell of plane 2 (the
+//               largest when a ring row not written by a game holds several), -1 when the plane is empty;
+//               move_count = m.  Rows P..G-1: empty board, player +1, last -1, count 0.
+//   rewrite     slice t of a job (t = drop + k, ring slot (slot + k) mod N), unroll step u, t + u < n:
+//               pol[u, :] = (float)pol_new[first + t + u - drop, :], val[u] = n_step_target(t + u) over the new values.
+//               Entries past the game, and every other ring array, are not touched.
+// One workgroup per row / per surviving slice.
+struct PositionRow {  // include/gmz.h's row record: 2 int32
+  int32_t slot, m;
+};
+static_assert(sizeof(PositionRow) == 8, "row record layout");
+
+struct PositionArgs {
+  const uint8_t *r_obs;
+  const PositionRow *rows;
+  int8_t *board;
+  int8_t *player;
+  int32_t *last;
+  int32_t *count;
+  int A, U, N, P;
+};
+
+__global__ __launch_bounds__(256) void k_replay_positions(const PositionArgs a) {
+  __shared__ int s_last;
+  const int r = (int)blockIdx.x, A = a.A, tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  int8_t *board = a.board + (size_t)r * A;
+  if (r >= a.P) {  // padding row
+    for (int c = tid; c < A; c += nt) board[c] = 0;
+    if (tid == 0) { a.player[r] = 1; a.last[r] = -1; a.count[r] = 0; }
+    return;
+  }
+  const PositionRow row = a.rows[r];
+  // the host validated the table it was given; a device copy that differs from it writes nothing
+  if (row.slot < 0 || row.slot >= a.N || row.m < 0 || row.m >= A) return;
+  const int8_t pl = (row.m & 1) ? -1 : 1;
+  const uint8_t *o = a.r_obs + (size_t)row.slot * (size_t)(a.U + 1) * 3 * A;
+  if (tid == 0) s_last = -1;
+  __syncthreads();
+  for (int c = tid; c < A; c += nt) {
+    board[c] = o[c] ? pl : (o[A + c] ? (int8_t)-pl : (int8_t)0);
+    if (o[2 * A + c]) atomicMax(&s_last, c);
+  }
+  __syncthreads();
+  if (tid == 0) { a.player[r] = pl; a.last[r] = s_last; a.count[r] = row.m; }
+}
+
+struct RewriteJob {  // include/gmz.h's job record: 6 int32
+  int32_t slot, kept, n, drop, winner, first;
+};
+static_assert(sizeof(RewriteJob) == 24, "job record layout");
+
+struct RewriteArgs {
+  const double *pol_new;
+  const float *val_new;
+  float *r_pol;
+  float *r_val;
+  const RewriteJob *jobs;
+  int A, U, n_steps, N, P, n_jobs;
+};
+
+__global__ __launch_bounds__(256) void k_replay_rewrite(const RewriteArgs a, const ReplayPow P) {
+  const int b = (int)blockIdx.x;
+  // last job whose first surviving slice is <= b
+  int lo = 0, hi = a.n_jobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.jobs[mid].first <= b) lo = mid; else hi = mid - 1;
+  }
+  const RewriteJob j = a.jobs[lo];
+  const int kk = b - j.first;
+  // the host validated the table it was given; a device copy that differs from it writes nothing
+  if (j.slot < 0 || j.slot >= a.N || j.kept < 1 || j.kept > a.N || j.n < 1 || j.drop < 0 || j.drop != j.n - j.kept ||
+      j.winner < -1 || j.winner > 1 || j.first < 0 || (long)j.first + j.kept > a.P || kk < 0 || kk >= j.kept)
+    return;
+  const int t0 = j.drop + kk, n = j.n, A = a.A, U = a.U;
+  const size_t ring = (size_t)((j.slot + (long)kk) % a.N);
+  const long row0 = (long)j.first - j.drop;  // staged row of position t: row0 + t, for t >= drop
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  for (int u = tid; u <= U; u += nt) {
+    const int t = t0 + u;
+    if (t < n) a.r_val[ring * (U + 1) + u] = n_step_target(P, a.n_steps, n, j.winner, t, a.val_new, row0);
+  }
+  float *pol = a.r_pol + ring * (size_t)(U + 1) * A;
+  for (int idx = tid; idx < (U + 1) * A; idx += nt) {
+    const int u = idx / A, c = idx - u * A, t = t0 + u;
+    if (t < n) pol[idx] = (float)a.pol_new[(size_t)(row0 + t) * A + c];
   }
 }
 
@@ -323,6 +424,27 @@ static inline void per_sizes(int count, long &ngroups, long &nchunks) {
 
 using namespace gmz;
 
+// host helpers of the entry points' validation
+static int short_capacity(const char *fn, const char *name, size_t have, size_t need) {
+  return fail(std::string(fn) + ": " + name + " of " + std::to_string(have) + " bytes is short of " +
+              std::to_string(need));
+}
+
+// ring slot runs as linear [begin, end) ranges: a run of `len` slots from `slot` that passes the ring's end is two
+static inline void add_span(std::vector<std::pair<long, long>> &spans, long slot, long len, long N) {
+  const long e = slot + len;
+  if (e <= N) spans.emplace_back(slot, e);
+  else { spans.emplace_back(slot, N); spans.emplace_back(0L, e - N); }
+}
+
+// the first ring slot two of the ranges share, or -1 (sorts the ranges)
+static inline long first_overlap(std::vector<std::pair<long, long>> &spans) {
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    if (spans[i].first < spans[i - 1].second) return spans[i].first;
+  return -1;
+}
+
 GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G, int L, const int8_t *hist_board_dev,
                                  const int8_t *hist_player_dev, const int32_t *hist_last_dev,
                                  const double *hist_policy_dev, const float *hist_value_dev,
@@ -367,14 +489,11 @@ GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G,
     total += kept;
     if (total > N)
       return fail("gmz_replay_ingest: the launch keeps more than the ring's N = " + std::to_string(N) + " slices");
-    const long e = j.slot + kept;
-    if (e <= N) spans.emplace_back(j.slot, e);
-    else { spans.emplace_back(j.slot, (long)N); spans.emplace_back(0L, e - N); }
+    add_span(spans, j.slot, kept, N);
   }
-  std::sort(spans.begin(), spans.end());
-  for (size_t i = 1; i < spans.size(); ++i)
-    if (spans[i].first < spans[i - 1].second)
-      return fail("gmz_replay_ingest: kept slices of two jobs overlap at ring slot " + std::to_string(spans[i].first));
+  const long shared = first_overlap(spans);
+  if (shared >= 0)
+    return fail("gmz_replay_ingest: kept slices of two jobs overlap at ring slot " + std::to_string(shared));
   ReplayArgs a;
   a.board = hist_board_dev; a.player = hist_player_dev; a.last = hist_last_dev; a.pol = hist_policy_dev;
   a.val = hist_value_dev; a.act = hist_action_dev;
@@ -386,6 +505,112 @@ GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G,
   ReplayPow P;
   for (int i = 0; i <= GMZ_REPLAY_MAX_N_STEPS; ++i) P.pw[i] = i <= n_steps ? discount_pow[i] : 0.0;
   hipLaunchKernelGGL(k_replay_ingest, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a, P);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_replay_positions(int board_size, int unroll, int N, const uint8_t *ring_obs_dev,
+                                    size_t ring_obs_bytes, const void *rows_host, int P, const void *rows_dev,
+                                    size_t rows_dev_bytes, int G, int8_t *board_out_dev, size_t board_out_bytes,
+                                    int8_t *player_out_dev, size_t player_out_bytes, int32_t *last_out_dev,
+                                    size_t last_out_bytes, int32_t *count_out_dev, size_t count_out_bytes,
+                                    void *stream) {
+  const char *fn = "gmz_replay_positions";
+  if (board_size < 5 || board_size > 22)
+    return fail("gmz_replay_positions: board_size " + std::to_string(board_size) + " outside 5..22");
+  if (unroll < 1) return fail("gmz_replay_positions: unroll " + std::to_string(unroll) + " < 1");
+  if (N < 1) return fail("gmz_replay_positions: N " + std::to_string(N) + " < 1");
+  if (G < 1) return fail("gmz_replay_positions: G " + std::to_string(G) + " < 1");
+  if (P < 1 || P > G) return fail("gmz_replay_positions: P " + std::to_string(P) + " outside 1..G = " + std::to_string(G));
+  if (!ring_obs_dev || !rows_host || !rows_dev) return fail("gmz_replay_positions: ring_obs_dev, rows_host or rows_dev is NULL");
+  if (!board_out_dev || !player_out_dev || !last_out_dev || !count_out_dev)
+    return fail("gmz_replay_positions: an output pointer is NULL");
+  const size_t A = (size_t)board_size * board_size, ng = (size_t)G;
+  if (ring_obs_bytes < (size_t)N * (size_t)(unroll + 1) * 3 * A)
+    return short_capacity(fn, "ring_obs", ring_obs_bytes, (size_t)N * (size_t)(unroll + 1) * 3 * A);
+  if (rows_dev_bytes < (size_t)P * sizeof(PositionRow))
+    return short_capacity(fn, "device row table", rows_dev_bytes, (size_t)P * sizeof(PositionRow));
+  if (board_out_bytes < ng * A) return short_capacity(fn, "board_out", board_out_bytes, ng * A);
+  if (player_out_bytes < ng) return short_capacity(fn, "player_out", player_out_bytes, ng);
+  if (last_out_bytes < ng * 4) return short_capacity(fn, "last_out", last_out_bytes, ng * 4);
+  if (count_out_bytes < ng * 4) return short_capacity(fn, "count_out", count_out_bytes, ng * 4);
+  const PositionRow *rows = (const PositionRow *)rows_host;
+  for (int i = 0; i < P; ++i) {
+    const std::string at = "gmz_replay_positions: row " + std::to_string(i) + ": ";
+    if (rows[i].slot < 0 || rows[i].slot >= N)
+      return fail(at + "ring slot " + std::to_string(rows[i].slot) + " outside 0.." + std::to_string(N - 1));
+    if (rows[i].m < 0 || rows[i].m >= (int)A)
+      return fail(at + "move count " + std::to_string(rows[i].m) + " outside 0.." + std::to_string(A - 1));
+  }
+  PositionArgs a;
+  a.r_obs = ring_obs_dev; a.rows = (const PositionRow *)rows_dev;
+  a.board = board_out_dev; a.player = player_out_dev; a.last = last_out_dev; a.count = count_out_dev;
+  a.A = (int)A; a.U = unroll; a.N = N; a.P = P;
+  hipLaunchKernelGGL(k_replay_positions, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, a);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
+GMZ_EXPORT int gmz_replay_rewrite(int board_size, int unroll, int n_steps, int N, float *ring_pol_dev,
+                                  size_t ring_pol_bytes, float *ring_val_dev, size_t ring_val_bytes,
+                                  const double *pol_new_dev, size_t pol_new_bytes, const float *val_new_dev,
+                                  size_t val_new_bytes, int P, const void *jobs_host, int n_jobs, const void *jobs_dev,
+                                  size_t jobs_dev_bytes, const double *discount_pow, void *stream) {
+  const char *fn = "gmz_replay_rewrite";
+  if (board_size < 5 || board_size > 22)
+    return fail("gmz_replay_rewrite: board_size " + std::to_string(board_size) + " outside 5..22");
+  if (unroll < 1) return fail("gmz_replay_rewrite: unroll " + std::to_string(unroll) + " < 1");
+  if (n_steps < 1 || n_steps > GMZ_REPLAY_MAX_N_STEPS)
+    return fail("gmz_replay_rewrite: n_steps " + std::to_string(n_steps) + " outside 1.." +
+                std::to_string(GMZ_REPLAY_MAX_N_STEPS));
+  if (N < 1) return fail("gmz_replay_rewrite: N " + std::to_string(N) + " < 1");
+  if (P < 0) return fail("gmz_replay_rewrite: P " + std::to_string(P) + " < 0");
+  if (n_jobs < 0) return fail("gmz_replay_rewrite: n_jobs < 0");
+  if (n_jobs == 0) return 0;
+  if (!jobs_host || !jobs_dev || !discount_pow) return fail("gmz_replay_rewrite: jobs_host, jobs_dev or discount_pow is NULL");
+  if (!ring_pol_dev || !ring_val_dev || !pol_new_dev || !val_new_dev)
+    return fail("gmz_replay_rewrite: a ring or staging pointer is NULL");
+  const size_t A = (size_t)board_size * board_size, U1 = (size_t)unroll + 1;
+  if (ring_pol_bytes < (size_t)N * U1 * A * sizeof(float))
+    return short_capacity(fn, "ring_pol", ring_pol_bytes, (size_t)N * U1 * A * sizeof(float));
+  if (ring_val_bytes < (size_t)N * U1 * sizeof(float))
+    return short_capacity(fn, "ring_val", ring_val_bytes, (size_t)N * U1 * sizeof(float));
+  if (pol_new_bytes < (size_t)P * A * sizeof(double))
+    return short_capacity(fn, "pol_new", pol_new_bytes, (size_t)P * A * sizeof(double));
+  if (val_new_bytes < (size_t)P * sizeof(float))
+    return short_capacity(fn, "val_new", val_new_bytes, (size_t)P * sizeof(float));
+  if (jobs_dev_bytes < (size_t)n_jobs * sizeof(RewriteJob))
+    return short_capacity(fn, "device job table", jobs_dev_bytes, (size_t)n_jobs * sizeof(RewriteJob));
+  const RewriteJob *jobs = (const RewriteJob *)jobs_host;
+  long total = 0;
+  std::vector<std::pair<long, long>> spans;
+  spans.reserve(2 * (size_t)n_jobs);
+  for (int i = 0; i < n_jobs; ++i) {
+    const RewriteJob &j = jobs[i];
+    const std::string at = "gmz_replay_rewrite: job " + std::to_string(i) + ": ";
+    if (j.slot < 0 || j.slot >= N)
+      return fail(at + "ring slot " + std::to_string(j.slot) + " outside 0.." + std::to_string(N - 1));
+    if (j.kept < 1) return fail(at + "kept " + std::to_string(j.kept) + " < 1");
+    if (j.kept > N) return fail(at + "kept " + std::to_string(j.kept) + " passes the ring's N = " + std::to_string(N));
+    if (j.n < 1 || j.drop < 0 || j.drop != j.n - j.kept)
+      return fail(at + "n " + std::to_string(j.n) + ", drop " + std::to_string(j.drop) + ", kept " +
+                  std::to_string(j.kept) + ": drop is not n - kept");
+    if (j.winner < -1 || j.winner > 1) return fail(at + "winner " + std::to_string(j.winner) + " outside -1..1");
+    if (j.first != total) return fail(at + "first " + std::to_string(j.first) + " is not the staged rows before it");
+    total += j.kept;
+    if (total > P)
+      return fail(at + "staged row " + std::to_string(total - 1) + " outside 0.." + std::to_string((long)P - 1));
+    add_span(spans, j.slot, j.kept, N);
+  }
+  const long shared = first_overlap(spans);
+  if (shared >= 0) return fail("gmz_replay_rewrite: the slices of two jobs overlap at ring slot " + std::to_string(shared));
+  RewriteArgs a;
+  a.pol_new = pol_new_dev; a.val_new = val_new_dev; a.r_pol = ring_pol_dev; a.r_val = ring_val_dev;
+  a.jobs = (const RewriteJob *)jobs_dev;
+  a.A = (int)A; a.U = unroll; a.n_steps = n_steps; a.N = N; a.P = P; a.n_jobs = n_jobs;
+  ReplayPow pw;
+  for (int i = 0; i <= GMZ_REPLAY_MAX_N_STEPS; ++i) pw.pw[i] = i <= n_steps ? discount_pow[i] : 0.0;
+  hipLaunchKernelGGL(k_replay_rewrite, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a, pw);
   GMZ_LAUNCH_CHECK();
   return 0;
 }

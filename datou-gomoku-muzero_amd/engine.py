@@ -191,6 +191,28 @@ class BatchedSelfPlayEngine:
         self._n_legal = (A - nz.numpy()).astype(np.int32)
         self._status_event = None
 
+    def set_positions_device(self, boards, players, last_moves, move_counts, n_legal_host):
+        """:meth:`set_positions` on device tensors (boards int8 [G, A] or [G, S, S], players int8 [G], last_moves
+        int32 [G], move_counts int32 [G], contiguous, on this engine's device): four device copies on the current
+        stream, no synchronisation and nothing read back.  The legal-move counts the host needs to size the searches
+        come from the caller: ``n_legal_host`` int [G], A minus the stones on each board (0 for a row that
+        set_active leaves out)."""
+        G, A, dev = self.G, self.A, self.device
+        want = ((boards, torch.int8, G * A), (players, torch.int8, G), (last_moves, torch.int32, G),
+                (move_counts, torch.int32, G))
+        for t, dt, numel in want:
+            if not torch.is_tensor(t) or t.dtype != dt or t.numel() != numel or t.device.type != dev.type \
+                    or not t.is_contiguous():
+                raise ValueError("set_positions_device: expected a contiguous %s tensor of %d elements on %s" %
+                                 (dt, numel, dev))
+        nl = np.array(n_legal_host, dtype=np.int32).reshape(-1)
+        if nl.shape != (G,) or nl.min() < 0 or nl.max() > A:
+            raise ValueError("set_positions_device: n_legal_host must hold %d counts in 0..%d" % (G, A))
+        check(self.lib.gmz_engine_copy_state(self.handle, 1, ptr(boards), ptr(players), ptr(last_moves),
+                                             ptr(move_counts), self._stream()))
+        self._n_legal = nl
+        self._status_event = None
+
     def set_active(self, mask=None):
         """Search only the games whose ``mask`` byte is nonzero (uint8/bool [G], host array; None: every game,
         the default).  An inactive game joins no wave and adds nothing to the tree counters; search() gives it
@@ -204,6 +226,19 @@ class BatchedSelfPlayEngine:
         d = torch.as_tensor(m.astype(np.uint8)).to(self.device)
         check(self.lib.gmz_engine_set_active(self.handle, ptr(d), self._stream()))
         d.record_stream(torch.cuda.current_stream(self.device))
+        self._active = m
+
+    def set_active_device(self, mask_dev, mask_host):
+        """:meth:`set_active` without the upload: ``mask_dev`` is the mask as a contiguous uint8 [G] tensor on this
+        engine's device (copied into the engine on the current stream), ``mask_host`` the same mask on the host,
+        which sizes the searches.  No synchronisation."""
+        if not torch.is_tensor(mask_dev) or mask_dev.dtype != torch.uint8 or mask_dev.numel() != self.G \
+                or mask_dev.device.type != self.device.type or not mask_dev.is_contiguous():
+            raise ValueError("set_active_device: expected a contiguous uint8 tensor of %d bytes on %s" %
+                             (self.G, self.device))
+        m = np.ascontiguousarray(np.asarray(mask_host).reshape(self.G) != 0)
+        check(self.lib.gmz_engine_set_active(self.handle, ptr(mask_dev), self._stream()))
+        mask_dev.record_stream(torch.cuda.current_stream(self.device))
         self._active = m
 
     def set_simulations(self, n):

@@ -16,6 +16,10 @@ own share of the work, time-sliced on its GPU:
               (gmz_replay_ingest, bit-identical; nothing but a job table crosses the bus);
               ``device_batches=True``: a training batch goes from the shard into the trainer's inputs by the
               PER draw and one gather launch in HIP (gmz_replay_per_sample, gmz_replay_gather; Trainer.step_from);
+  re-analysis ``reanalyser`` (reanalysis.RingReanalyser) and ``reanalyse_per_iter`` > 0: after an iteration's moves
+              that many passes search the shard's oldest-searched games again with the current network and
+              rewrite their policy and value targets in the ring (MuZero Reanalyse; off by default); each rank
+              re-analyses its own shard, no collectives;
   training    data-parallel: each rank samples its batch from its own shard; gradients are averaged
               by one flat-bucket all-reduce per step (RCCL over xGMI); PER (sharded):
               IS weights from the global slice count (all-reduce SUM) normalised by the global batch
@@ -131,7 +135,7 @@ class C4Loop:
 
     def __init__(self, selfplay, trainer, buffer, cfg, batch_size, dist=None, moves_per_iter=1,
                  train_steps_per_iter=1, model_update_interval=1000, seed=0, device="cuda", concurrent=False,
-                 device_ingest=False, device_batches=False):
+                 device_ingest=False, device_batches=False, reanalyser=None, reanalyse_per_iter=0):
         self.sp, self.tr, self.rb, self.cfg = selfplay, trainer, buffer, cfg
         self.B, self.dist = int(batch_size), dist
         self.moves_per_iter, self.train_steps_per_iter = int(moves_per_iter), int(train_steps_per_iter)
@@ -150,6 +154,12 @@ class C4Loop:
         # the self-play engines fork every move from this stream: weight swaps are enqueued on it
         self.sp_stream = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
         self._train_done = None
+        # re-analysis of the shard's own games: passes per iteration, after its moves; ring reads and writes on the
+        # stream of every other ring operation, the searches on the self-play stream
+        self.ra, self.reanalyse_per_iter = reanalyser, int(reanalyse_per_iter) if reanalyser is not None else 0
+        self.reanalysed_games = self.reanalysed_positions = 0
+        if self.ra is not None:
+            self.ra.ring_stream = self.train_stream
         # device_ingest: finished games go from the self-play history to the shard in HIP (one launch per
         # move, GameHistory.ingest) on the stream of every other ring operation; off = the host path
         self.device_ingest = bool(device_ingest)
@@ -181,7 +191,8 @@ class C4Loop:
             g, winner, n, mf, mt = item[:5]
             if not self.device_ingest:  # device_ingest: SelfPlay.step has written the slices already
                 arrs = slices_from_game(*item[5:], winner, c.BOARD_SIZE, c.DISCOUNT, c.N_STEPS, c.NUM_UNROLL_STEPS)
-                self.rb.add_arrays(*arrs)
+                # the directory entry re-analysis reads: the stones under the first recorded position, this step
+                self.rb.add_arrays(*arrs, game=(winner, int(np.count_nonzero(item[5][0])), self.train_steps))
             self.games += 1
             self.slices += n
             self.game_lengths.append(n)
@@ -216,8 +227,12 @@ class C4Loop:
                 self.sp_stream.wait_stream(cur)
             with torch.cuda.stream(self.sp_stream):
                 self.sp.load_weights(sd)
+                if self.ra is not None:
+                    self.ra.load_weights(sd)
         else:
             self.sp.load_weights(sd)
+            if self.ra is not None:
+                self.ra.load_weights(sd)
         self.weight_pushes += 1
 
     def train_step(self):
@@ -229,6 +244,7 @@ class C4Loop:
         self.rb.update_priorities(idx, td, dist=self.dist)
         self.last_logs = logs
         self.train_steps += 1
+        self.rb.step = self.train_steps  # the version of the games ingested from now on
         if self.train_steps % self.model_update_interval == 0:
             self.push_weights()
 
@@ -238,6 +254,7 @@ class C4Loop:
             return self._iteration_concurrent()
         for _ in range(self.moves_per_iter):
             self._add_games(self.sp.step())
+        self._reanalyse()
         if self.train_steps_per_iter > 0 and self._all_ready():
             for _ in range(self.train_steps_per_iter):
                 self.train_step()
@@ -256,8 +273,17 @@ class C4Loop:
             done += self.sp.step()
         with torch.cuda.stream(ts):  # after this iteration's steps on the same stream
             self._add_games(done)
+        self._reanalyse()  # ring work on the train stream after the adds, searches on this one
         self._train_done = torch.cuda.Event()
         self._train_done.record(ts)
+
+    def _reanalyse(self):
+        """``reanalyse_per_iter`` passes over the shard at the current trainer step.  One host call each, with no
+        append inside it: on the ring's stream the rewrite lands before any later append can recycle its slots."""
+        for _ in range(self.reanalyse_per_iter):
+            g, p = self.ra.pass_(self.train_steps)
+            self.reanalysed_games += g
+            self.reanalysed_positions += p
 
     def run(self, iterations):
         for _ in range(iterations):
@@ -268,7 +294,8 @@ class C4Loop:
 
     def stats(self):
         return {"moves": int(getattr(self.sp, "moves", 0)), "games": self.games, "slices": self.slices,
-                "train_steps": self.train_steps, "weight_pushes": self.weight_pushes, "buffer": len(self.rb)}
+                "train_steps": self.train_steps, "weight_pushes": self.weight_pushes, "buffer": len(self.rb),
+                "reanalysed_games": self.reanalysed_games, "reanalysed_positions": self.reanalysed_positions}
 
 
 def run_c4(args, rank, world, dist, backend, log=print):
@@ -276,7 +303,8 @@ def run_c4(args, rank, world, dist, backend, log=print):
     from . import trainer as T, weights as W
     from .config import GmzConfig
     torch.backends.cudnn.benchmark = True
-    cfg = GmzConfig(BOARD_SIZE=args.size, NUM_SIMULATIONS=args.sims, NUM_RES_BLOCKS=args.blocks)
+    cfg = GmzConfig(BOARD_SIZE=args.size, NUM_SIMULATIONS=args.sims, NUM_RES_BLOCKS=args.blocks,
+                    REANALYSIS_AGE_THRESHOLD=int(getattr(args, "loop_reanalyse_age", 900)))
     tcfg = T.TrainConfig(BOARD_SIZE=args.size, NUM_RES_BLOCKS=args.blocks, PHYSICAL_BATCH_SIZE=args.trainer_batch,
                          TRAIN_BUFFER_SIZE=args.loop_buffer, ENABLE_PER=True,
                          MODEL_UPDATE_INTERVAL=args.loop_update_interval)
@@ -294,12 +322,20 @@ def run_c4(args, rank, world, dist, backend, log=print):
         from .weights import synthetic_slices
         rb.add_arrays(*synthetic_slices(args.loop_prefill, args.size, tcfg.NUM_UNROLL_STEPS,
                                         np.random.RandomState(args.seed + 31 * rank)))
+    ra, ra_passes = None, int(getattr(args, "loop_reanalyse", 0))
+    if ra_passes > 0:  # re-analysis of the shard's own games (off unless asked for)
+        from .reanalysis import RingReanalyser
+        ra = RingReanalyser(cfg, rb, sd, num_games=int(getattr(args, "loop_reanalyse_games", 256)),
+                            max_positions=getattr(args, "loop_reanalyse_positions", None),
+                            seed=args.seed + 104729 * (rank + 1), precision=getattr(args, "precision", "fp16"))
+        ra.host = ra.host or bool(getattr(args, "loop_reanalyse_host", False))  # the A/B's host path
     loop = C4Loop(sp, tr, rb, tcfg, args.trainer_batch, dist=dist if world > 1 else None,
                   moves_per_iter=args.loop_moves_per_iter, train_steps_per_iter=args.loop_train_per_iter,
                   model_update_interval=args.loop_update_interval, seed=args.seed,
                   concurrent=getattr(args, "loop_concurrent", False),
                   device_ingest=getattr(args, "loop_device_ingest", False),
-                  device_batches=getattr(args, "loop_device_batches", False))
+                  device_batches=getattr(args, "loop_device_batches", False), reanalyser=ra,
+                  reanalyse_per_iter=ra_passes)
     t_w = time.perf_counter()
     loop.run(args.loop_warmup)
     torch.cuda.synchronize()
@@ -316,6 +352,8 @@ def run_c4(args, rank, world, dist, backend, log=print):
     dt = time.perf_counter() - t0
     s1 = loop.stats()
     d = {k: s1[k] - s0[k] for k in ("moves", "games", "slices", "train_steps", "weight_pushes")}
+    if ra is not None:
+        d.update({k: s1[k] - s0[k] for k in ("reanalysed_games", "reanalysed_positions")})
     d["buffer"] = s1["buffer"]
     # one ModelWeightsUpdate (workers.py:587-593) on its own, after the timed window: rank 0's trainer
     # weights -> broadcast -> every rank's inference network; the timed window runs the reference's
@@ -330,4 +368,6 @@ def run_c4(args, rank, world, dist, backend, log=print):
     torch.cuda.synchronize()
     d["push_ms"] = (time.perf_counter() - t_p) / n_push * 1e3
     sp.close()
+    if ra is not None:
+        ra.close()
     return d, dt

@@ -13,7 +13,13 @@ padded with empty boards whose results are dropped).  The missed-win census runs
 the batched winning-move scan (``gmz_game_winning_scan``), one launch per batch.  The per-position
 results are those of the reference's sequential searches with the same Gumbel noise (tested against
 the oracle in tests/test_reanalysis_gpu.py).
+
+``RingReanalyser`` is the same re-search for the composed loop (loop.C4Loop): its games are the ones in the
+trainer's device replay ring (trainer.ReplayBuffer.games), decoded from the ring's own planes and rewritten in
+place by two HIP launches (gmz_replay_positions, gmz_replay_rewrite), so the batches the trainer draws carry
+targets of the current network.  The missed-win census stays with the database path.
 """
+import contextlib
 from dataclasses import dataclass
 
 import numpy as np
@@ -120,6 +126,206 @@ class Reanalyser:
             out.append(ReanalysedGame(p, v, targets, cf, of, ct, ot))
             off += n
         return out
+
+
+def ring_rows(entries, N):
+    """The (ring slot, move count) of every surviving slice of ``entries`` (trainer.RingGame) in staging order (game
+    after game, positions drop..n-1) -> int32 [P, 2]; the move count of position t is start + t."""
+    rows = [np.stack([(e.slot + np.arange(e.kept)) % N, e.start + e.drop + np.arange(e.kept)], 1) for e in entries]
+    return np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 2), np.int32)
+
+
+def ring_positions_host(rb, rows):
+    """The host's decode of ring slices into search positions (the twin of gmz_replay_positions): ``rows`` int32
+    [P, 2] of (slot, move count) -> boards int8 [P, S, S], players int8 [P] (+1 on even counts), last_moves int32 [P]
+    (-1: none), move_counts int32 [P], from the step-0 planes of ``rb.obs``."""
+    S = int(rb.cfg.BOARD_SIZE)
+    P = len(rows)
+    idx = torch.as_tensor(rows[:, 0].astype(np.int64)).to(rb.obs.device)
+    planes = rb.obs[idx, 0].cpu().numpy().reshape(P, 3, S * S)
+    mc = rows[:, 1].astype(np.int32)
+    players = np.where(mc % 2 == 0, 1, -1).astype(np.int8)
+    boards = (planes[:, 0] != 0) * players[:, None] - (planes[:, 1] != 0) * players[:, None]
+    last = np.where(planes[:, 2].any(1), planes[:, 2].argmax(1), -1).astype(np.int32)
+    return boards.astype(np.int8).reshape(P, S, S), players, last, mc
+
+
+class RingReanalyser:
+    """MuZero Reanalyse on the trainer's replay ring: the games the ring holds (trainer.ReplayBuffer.games) are
+    searched again with the current network and their policy and n-step value targets rewritten in place.
+
+    It owns a network (``state_dict``: network.GomokuNetHip; None: the engine's hash backend) and an engine of
+    ``num_games`` slots of its own (the self-play engine's boards and trees are live), and staging for
+    ``max_positions`` positions (default 4 * num_games; at least A, so that any one game fits).  With the ring on
+    the GPU a pass never leaves the device: gmz_replay_positions decodes ring slices into the engine's inputs
+    (BatchedSelfPlayEngine.set_positions_device), the searches' policies and values are copied into the staging, and
+    one gmz_replay_rewrite writes the targets.  Ring reads and writes go on ``ring_stream`` (None: the current
+    stream; the loop's train stream in concurrent mode: the stream of every other ring operation), the searches on
+    the current stream, events between the two.  The host never waits for the work a pass enqueues, nor for anything
+    in front of it on either stream: the padding mask of a short chunk is built on the device
+    (set_active_device), and the one host wait is for the table set of two passes back, an event long passed
+    (as GameHistory's job tables).  An explicit ``gumbel`` (tests) is a pageable upload per chunk and does block.
+    With the ring on the CPU (or ``host`` set) the same pass goes through the host (:meth:`pass_host`)."""
+
+    def __init__(self, cfg, buffer, state_dict=None, num_games=256, max_positions=None, seed=0, precision="fp16"):
+        from . import engine as E
+        from .config import from_any
+        c = self.cfg = from_any(cfg)
+        rc = buffer.cfg
+        if (c.BOARD_SIZE, c.NUM_UNROLL_STEPS) != (rc.BOARD_SIZE, rc.NUM_UNROLL_STEPS):
+            raise ValueError("RingReanalyser: the engine's config and the buffer's disagree on the slices' geometry")
+        self.rb, self.G, self.A = buffer, int(num_games), int(c.ACTION_SPACE_SIZE)
+        self.max_positions = int(4 * self.G if max_positions is None else max_positions)
+        if self.max_positions < self.A:
+            raise ValueError("RingReanalyser: max_positions %d cannot hold one game of %d moves" %
+                             (self.max_positions, self.A))
+        self.net = None
+        if state_dict is not None:
+            from . import network as N
+            self.net = N.GomokuNetHip(state_dict, c, num_slots=E.hidden_slots(c, self.G), max_rows=self.G,
+                                      precision=precision)
+        self.eng = E.BatchedSelfPlayEngine(c, num_games=self.G, net=self.net, seed=seed)
+        self.searcher = Reanalyser(self.eng)  # the host path's batched searches
+        dev, G, A, M = self.eng.device, self.G, self.A, self.max_positions
+        self.ring_stream = None
+        self.host = buffer.obs.device.type != "cuda"  # True: every pass goes through pass_host (a CPU ring; A/B)
+        self.games = self.positions = 0
+        self.last_pass = ([], 0)
+        self.pol_new = torch.zeros(M, A, dtype=torch.float64, device=dev)
+        self.val_new = torch.zeros(M, dtype=torch.float32, device=dev)
+        self.board = torch.zeros(G, A, dtype=torch.int8, device=dev)
+        self.player = torch.ones(G, dtype=torch.int8, device=dev)
+        self.last = torch.full((G,), -1, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(G, dtype=torch.int32, device=dev)
+        self._row = torch.arange(G, device=dev)  # row < n: the active mask of a chunk of n positions, made on the device
+        self._tables = None     # pinned + device (row table, job table), rotating behind events
+        self._tk = 0
+        self._loaded = None     # the engine's last read of board/player/last/count (the next decode waits for it)
+        self._rewritten = None  # the last rewrite's read of the staging (the next pass's copies wait for it)
+
+    def load_weights(self, sd):
+        if self.net is not None:
+            self.net.load_state_dict(sd)
+
+    def close(self):
+        self.eng.close()
+
+    def _take(self, step, age):
+        take, P = [], 0
+        for e in self.rb.eligible(step, self.cfg.REANALYSIS_AGE_THRESHOLD if age is None else age):
+            if P + e.kept > self.max_positions:
+                break
+            take.append(e)
+            P += e.kept
+        return take, P
+
+    def _job_tables(self):
+        """The next (pinned rows, device rows, pinned jobs, device jobs, event) of the rotation; waits until the
+        launches that last read this set have passed (two passes back: long passed)."""
+        if self._tables is None:
+            M, dev = self.max_positions, self.eng.device
+            self._tables = [[torch.zeros(M, 2, dtype=torch.int32).pin_memory(),
+                             torch.zeros(M, 2, dtype=torch.int32, device=dev),
+                             torch.zeros(M, 6, dtype=torch.int32).pin_memory(),
+                             torch.zeros(M, 6, dtype=torch.int32, device=dev), None] for _ in range(2)]
+        t = self._tables[self._tk & 1]
+        self._tk += 1
+        if t[4] is not None:
+            t[4].synchronize()
+        return t
+
+    def pass_(self, step, age=None, gumbel=None):
+        """One re-analysis pass at trainer step ``step``: the eligible games (version <= step - age; ``age`` None =
+        cfg.REANALYSIS_AGE_THRESHOLD), oldest search first, as many as the staging holds, are searched position by
+        position in chunks of ``num_games`` and their ring targets rewritten; their entries' version becomes
+        ``step``.  ``gumbel``: optional f64 [positions, A] root noise in staging order (default: the engine's device
+        noise).  Returns (games, positions)."""
+        if self.host:
+            return self.pass_host(step, age, gumbel)
+        from . import _lib as L
+        take, P = self._take(step, age)
+        if not take:
+            return 0, 0
+        rb, eng, G, A = self.rb, self.eng, self.G, self.A
+        dev = eng.device
+        cur = torch.cuda.current_stream(dev)
+        rs = self.ring_stream if self.ring_stream is not None else cur
+        two = rs != cur
+        rows = ring_rows(take, rb.N)
+        kept = np.array([e.kept for e in take], dtype=np.int64)
+        jobs = np.stack([[e.slot, e.kept, e.n, e.drop, e.winner, 0] for e in take]).astype(np.int32)
+        jobs[:, 5] = np.cumsum(kept) - kept
+        J = len(take)
+        tab = self._job_tables()
+        rows_pin, rows_dev, jobs_pin, jobs_dev = tab[:4]
+        rows_pin[:P] = torch.from_numpy(rows)
+        jobs_pin[:J] = torch.from_numpy(jobs)
+        with torch.cuda.stream(rs):
+            rows_dev[:P].copy_(rows_pin[:P], non_blocking=True)
+            jobs_dev[:J].copy_(jobs_pin[:J], non_blocking=True)
+        if two and self._rewritten is not None:
+            cur.wait_event(self._rewritten)  # the staging is free again
+        for lo in range(0, P, G):
+            n = min(G, P - lo)
+            if two and self._loaded is not None:
+                rs.wait_event(self._loaded)  # the engine has taken the previous chunk's positions
+            L.replay_positions(rb, rows_pin[lo:lo + n], rows_dev[lo:lo + n], n, self.board, self.player, self.last,
+                               self.count, stream=rs)
+            if two:
+                ev = torch.cuda.Event()
+                ev.record(rs)
+                cur.wait_event(ev)
+            legal = np.zeros(G, np.int32)
+            legal[:n] = A - rows[lo:lo + n, 1]
+            eng.set_positions_device(self.board, self.player, self.last, self.count, legal)
+            if two:
+                self._loaded = torch.cuda.Event()
+                self._loaded.record(cur)
+            if n == G:
+                eng.set_active(None)
+            else:  # the padding rows stay out of the search; no upload, so nothing blocks the host
+                eng.set_active_device((self._row < n).to(torch.uint8), np.arange(G) < n)
+            g = None
+            if gumbel is not None:
+                g = np.zeros((G, A), np.float64)
+                g[:n] = gumbel[lo:lo + n]
+            pol, val, _ = eng.search(gumbel=g)
+            self.pol_new[lo:lo + n].copy_(pol[:n])
+            self.val_new[lo:lo + n].copy_(val[:n])
+        if two:
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            rs.wait_event(ev)
+        L.replay_rewrite(rb, self.pol_new, self.val_new, P, jobs_pin, jobs_dev, J, stream=rs)
+        done = torch.cuda.Event()
+        done.record(rs)
+        tab[4] = self._rewritten = done
+        return self._stamp(take, P, step)
+
+    def pass_host(self, step, age=None, gumbel=None):
+        """:meth:`pass_` through host memory: the planes are read back and decoded on the host, the positions go
+        through Reanalyser.search_positions (an upload, a synchronise and a read-back per chunk) and the targets
+        through ReplayBuffer.rewrite_games_host.  The same games, searches and targets as the device path."""
+        take, P = self._take(step, age)
+        if not take:
+            return 0, 0
+        on_ring = (lambda: torch.cuda.stream(self.ring_stream)) if self.ring_stream is not None else contextlib.nullcontext
+        with on_ring():
+            pos = ring_positions_host(self.rb, ring_rows(take, self.rb.N))
+        self.eng.set_active(None)  # search_positions pads with empty boards and searches every row
+        pol, val, _, _ = self.searcher.search_positions(*pos, gumbel=gumbel)
+        with on_ring():
+            self.rb.rewrite_games_host(take, pol, val)
+        return self._stamp(take, P, step)
+
+    def _stamp(self, take, P, step):
+        for e in take:
+            e.version = int(step)
+        # (after a device pass rows 0..P-1 of pol_new / val_new hold these games' results until the next pass)
+        self.last_pass = (take, P)
+        self.games += len(take)
+        self.positions += P
+        return len(take), P
 
 
 def reanalysis_step(reanalyser, store, current_trainer_step, cfg, max_games=64, ui_queue=None, gumbel=None):

@@ -2035,6 +2035,25 @@ def muzero_loss(model, target_model, batch, is_weights, cfg, k=None, flip=None, 
 
 
 # ------------------------------------------------------------------------------ replay
+class RingGame:
+    """One game with slices in a ReplayBuffer's ring (an entry of its game directory): ``slot`` the ring slot of its
+    oldest surviving slice (slice k of the survivors is at (slot + k) mod N), ``kept`` surviving slices, ``n`` moves
+    recorded (``drop`` = n - kept slices lost from the front), ``winner``, ``start`` stones on the board at its first
+    recorded position, ``version`` the trainer step at which its targets were last searched, ``seq`` append order."""
+    __slots__ = ("slot", "kept", "n", "winner", "start", "version", "seq")
+
+    def __init__(self, slot, kept, n, winner, start, version, seq):
+        self.slot, self.kept, self.n, self.winner = int(slot), int(kept), int(n), int(winner)
+        self.start, self.version, self.seq = int(start), int(version), int(seq)
+
+    @property
+    def drop(self):
+        return self.n - self.kept
+
+    def __repr__(self):
+        return "RingGame(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k in self.__slots__)
+
+
 class ReplayBuffer:
     """Device-resident ring of TrainingSlices with the sampling of replay_buffer.py:44-106.
 
@@ -2042,7 +2061,12 @@ class ReplayBuffer:
     rewards f32, policies f32 [N, U+1, A], values f32; priorities f32 [N].  Sampling: uniform
     without replacement (ENABLE_PER off, the reference default) or stratified proportional PER
     (segment i of the total priority, one uniform draw each; prefix sums + binary search give the
-    same leaf as the reference's sum-tree descent), IS weights (count * p / total)^-beta / max."""
+    same leaf as the reference's sum-tree descent), IS weights (count * p / total)^-beta / max.
+
+    ``games`` is the host-side directory of the games whose slices the ring holds (RingGame, oldest first): made by
+    :meth:`ingest_history` and by :meth:`add_arrays` with ``game=``, trimmed by every append, read by re-analysis
+    (:meth:`eligible`, reanalysis.RingReanalyser).  Slices appended without it (:meth:`add`, synthetic prefill) have
+    no entry and are never re-analysed."""
 
     def __init__(self, cfg, capacity=None, device="cuda"):
         c = cfg
@@ -2057,6 +2081,8 @@ class ReplayBuffer:
         self.prio = torch.zeros(self.N, dtype=torch.float32, device=d)
         self.ptr, self.count, self.max_priority, self.device = 0, 0, 1.0, d
         self._per_ws = None  # gmz_replay_per_sample's workspace (sample_indices(hip=True)), built at first use
+        self.games, self._seq = [], 0  # the game directory (RingGame, oldest first) and its append counter
+        self.step = 0  # the trainer step ingest_history stamps on new entries (the loop keeps it current)
 
     def __len__(self):
         return self.count
@@ -2067,6 +2093,7 @@ class ReplayBuffer:
         n = len(slices)
         if n == 0:
             return
+        self._trim(n)
         idx = (torch.arange(n) + self.ptr) % self.N
         st = lambda f, dt: torch.from_numpy(np.stack([np.asarray(getattr(s, f)) for s in slices]).astype(dt))  # noqa: E731
         self.obs[idx] = st("observation", np.uint8).to(self.device)
@@ -2081,15 +2108,20 @@ class ReplayBuffer:
         self.ptr = (self.ptr + n) % self.N
         self.count = min(self.N, self.count + n)
 
-    def add_arrays(self, obs, act, rew, pol, val):
+    def add_arrays(self, obs, act, rew, pol, val, game=None):
         """Append n slices given as stacked arrays/tensors (obs [n,U+1,3,H,W] 0/1, act [n,U] int,
-        rew [n,U], pol [n,U+1,A], val [n,U+1]); same ring semantics as :meth:`add`."""
-        n = int(obs.shape[0])
+        rew [n,U], pol [n,U+1,A], val [n,U+1]); same ring semantics as :meth:`add`.  ``game`` = (winner, start,
+        version): the slices are one whole game's, in move order (loop.slices_from_game), and it gets a directory
+        entry (RingGame); without it no entry is made."""
+        n = moves = int(obs.shape[0])
         if n == 0:
             return
         if n > self.N:  # only the newest N survive the ring
             obs, act, rew, pol, val = obs[-self.N:], act[-self.N:], rew[-self.N:], pol[-self.N:], val[-self.N:]
             n = self.N
+        self._trim(n)
+        if game is not None:
+            self._note_game(self.ptr, n, moves, *game)
         idx = ((torch.arange(n) + self.ptr) % self.N).to(self.device)
         def dv(x, dt):
             if isinstance(x, np.ndarray) and not x.flags.writeable:
@@ -2106,6 +2138,68 @@ class ReplayBuffer:
             self.prio[idx] = 1.0
         self.ptr = (self.ptr + n) % self.N
         self.count = min(self.N, self.count + n)
+
+    # ---------------------------------------------------------------- game directory
+    def _trim(self, k):
+        """The directory before ``k`` slices are appended at ``ptr``: the slots they overwrite hold the oldest
+        slices of the oldest games (worker.replay_jobs), so those entries' slot, kept and drop advance, and an entry
+        with nothing left goes.  A trimmed game stays whole for re-analysis: its surviving slices t >= drop read
+        positions t..t+U and values t+N_STEPS only."""
+        N, k, gone = self.N, min(int(k), self.N), 0
+        for e in self.games:
+            d = (e.slot - self.ptr) % N  # the entry's oldest slice is the d-th slot the append writes
+            if d >= k:
+                break
+            over = min(k - d, e.kept)
+            e.slot, e.kept = (e.slot + over) % N, e.kept - over
+            if e.kept:
+                break
+            gone += 1
+        del self.games[:gone]
+
+    def _note_game(self, slot, kept, n, winner, start, version):
+        self.games.append(RingGame(slot, kept, n, winner, start, version, self._seq))
+        self._seq += 1
+
+    def note_jobs(self, jobs, appended, version=None):
+        """The directory's half of an ingest, before ``ptr`` moves: ``jobs`` is worker.replay_jobs' table (int32
+        [J, 8]: game, bank, row0, n, winner, drop, slot, first; a game's first recorded row is its ``start``) of
+        games that append ``appended`` slices in all at ``ptr``."""
+        self._trim(appended)
+        v = self.step if version is None else version
+        for (_, _, row0, n, winner, drop, slot, _) in np.asarray(jobs).reshape(-1, 8).tolist():
+            self._note_game(slot, n - drop, n, winner, row0, v)
+
+    def eligible(self, step, age):
+        """The games whose targets are at least ``age`` trainer steps old at ``step`` (version <= step - age), oldest
+        search first: ordered by (version, seq)."""
+        lim = int(step) - int(age)
+        return sorted((e for e in self.games if e.version <= lim), key=lambda e: (e.version, e.seq))
+
+    def rewrite_games_host(self, entries, pol_new, val_new):
+        """New search results into the ring slices of ``entries`` (RingGame, in staging order) on the host:
+        ``pol_new`` f64 [P, A] and ``val_new`` f32 [P] hold, game after game, the rows of positions drop..n-1.  Each
+        game's policy and n-step value targets are loop.slices_from_game's for the new policies and values (the
+        positions before ``drop`` reach no surviving slice), assigned to its ring rows by torch indexing; planes,
+        actions, rewards and priorities stay.  The reference of gmz_replay_rewrite, and the path of a ring on the
+        CPU."""
+        from .loop import slices_from_game
+        c = self.cfg
+        H, A = int(c.BOARD_SIZE), int(c.BOARD_SIZE) ** 2
+        pol_new = np.asarray(pol_new, dtype=np.float64).reshape(-1, A)
+        val_new = np.asarray(val_new, dtype=np.float32).reshape(-1)
+        first = 0
+        for e in entries:
+            n, drop = e.n, e.drop
+            pols, vals = np.zeros((n, A), np.float64), np.zeros(n, np.float32)
+            pols[drop:], vals[drop:] = pol_new[first:first + e.kept], val_new[first:first + e.kept]
+            _, _, _, p, v = slices_from_game(np.zeros((n, A), np.int8), np.ones(n, np.int8), np.full(n, -1, np.int32),
+                                             pols, vals, np.zeros(n, np.int32), e.winner, H, c.DISCOUNT, c.N_STEPS,
+                                             c.NUM_UNROLL_STEPS)
+            idx = ((torch.arange(e.kept) + e.slot) % self.N).to(self.device)
+            self.pol[idx] = torch.from_numpy(np.array(p[drop:])).to(self.device)  # (copies: the views may be read-only)
+            self.val[idx] = torch.from_numpy(np.array(v[drop:])).to(self.device)
+            first += e.kept
 
     def admission_priority(self):
         """The priority of newly added slices as a device f32 scalar, or None for 1.0 (PER off, or no
@@ -2133,7 +2227,7 @@ class ReplayBuffer:
             raise ValueError("ring of %d slices, %d unroll steps: smaller than one slice" % (self.N, U))
         if hist.board.device != self.obs.device:
             raise ValueError("history on %s, ring on %s" % (hist.board.device, self.obs.device))
-        return hist.ingest(sn, self, games=games)
+        return hist.ingest(sn, self, games=games)  # (its job table makes the games' directory entries: note_jobs)
 
     def sample(self, B, rng=np.random, dist=None):
         """replay_buffer.py:58-94.  ``dist``: torch.distributed when this buffer is one rank's shard of

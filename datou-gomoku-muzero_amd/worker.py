@@ -254,6 +254,8 @@ class GameHistory:
             ev = torch.cuda.Event()
             ev.record(stream)
             tab[2] = self._ingest_ev = ev
+        # the ring's game directory (re-analysis): trimmed by what the games append, then one entry per job
+        rb.note_jobs(jobs, sum(min(int(x[3]), int(rb.N)) for x in games))
         rb.ptr, rb.count = new_ptr, new_count
         return [(g, w, n, mf, mt) for (g, _, _, n, w, mf, mt) in games]
 

@@ -640,6 +640,42 @@ int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G, int L, con
                       float *ring_prio_dev, int N, const void *jobs_host, int n_jobs, const void *jobs_dev,
                       size_t jobs_dev_bytes, const double *discount_pow, const float *priority_dev, void *stream);
 
+/* ------------------------------------------------------------------ ring re-analysis (ring -> engine -> ring) */
+/* Games that are already in the ring are searched again with the current network (reanalysis.RingReanalyser): one
+ * launch turns ring slices into engine positions, and after the searches one launch turns the new policies and
+ * values into the slices' targets.  Ring as above.  Both tables are given twice, as gmz_replay_ingest's is: the host
+ * copy is validated before anything is launched, the kernel reads the device copy (the caller's copy of the same
+ * table, ordered before the call on `stream`) and writes nothing for a record that fails the same checks.
+ *
+ * gmz_replay_positions: row record (8 bytes, 2 int32): slot (ring slot of a slice), m (stones on the board at the
+ * slice's first position).  Rows 0..P-1 of the outputs (the arguments of gmz_engine_copy_state(h, 1, ...), G rows
+ * each, every output with its capacity in bytes) are decoded from planes obs[slot][0]: player = +1 for even m, -1 for
+ * odd m; board cell = player where the own plane is 1, -player where the opponent plane is 1, else 0; last = the
+ * set cell of the last-move plane, -1 when it is empty; move_count = m.  Rows P..G-1 are empty boards: player +1,
+ * last -1, count 0.  One workgroup per row.  Refused, nothing launched: board_size outside 5..22, unroll < 1, N < 1,
+ * G < 1, P outside 1..G, a NULL pointer, a short ring, table or output, slot outside 0..N-1, m outside 0..A-1. */
+int gmz_replay_positions(int board_size, int unroll, int N, const uint8_t *ring_obs_dev, size_t ring_obs_bytes,
+                         const void *rows_host, int P, const void *rows_dev, size_t rows_dev_bytes, int G,
+                         int8_t *board_out_dev, size_t board_out_bytes, int8_t *player_out_dev, size_t player_out_bytes,
+                         int32_t *last_out_dev, size_t last_out_bytes, int32_t *count_out_dev, size_t count_out_bytes,
+                         void *stream);
+/* gmz_replay_rewrite: job record (24 bytes, 6 int32), one per game: slot (ring slot of its oldest surviving slice;
+ * surviving slice k is at (slot + k) mod N), kept (surviving slices), n (recorded moves), drop (= n - kept: slices
+ * lost from the front), winner (+1 / -1, 0 draw), first (staged rows of the jobs before it).  Staged results:
+ * pol_new_dev f64 [P][A], val_new_dev f32 [P]; the row of position t (drop <= t < n) of a job is first + t - drop.
+ * For every surviving slice t and every unroll step u <= U with t + u < n:
+ *   ring_pol[slot(t)][u][:] = (float)pol_new[t + u]    ring_val[slot(t)][u] = the n-step target of position t + u
+ * over the rewards (n, winner) determine and the new values, by gmz_replay_ingest's formula in its operation order
+ * (discount_pow as there).  Entries past the game, and obs, act, rew and prio, are not touched.  One workgroup per
+ * surviving slice.  Refused, nothing launched: board_size, unroll, n_steps as for the ingest, a NULL pointer, a
+ * short ring, staging or table capacity, slot outside 0..N-1, kept outside 1..N, drop != n - kept, winner outside
+ * -1..1, a wrong `first`, a staged row outside 0..P-1, jobs whose slot runs overlap.  n_jobs == 0 launches nothing
+ * and succeeds. */
+int gmz_replay_rewrite(int board_size, int unroll, int n_steps, int N, float *ring_pol_dev, size_t ring_pol_bytes,
+                       float *ring_val_dev, size_t ring_val_bytes, const double *pol_new_dev, size_t pol_new_bytes,
+                       const float *val_new_dev, size_t val_new_bytes, int P, const void *jobs_host, int n_jobs,
+                       const void *jobs_dev, size_t jobs_dev_bytes, const double *discount_pow, void *stream);
+
 /* ------------------------------------------------------------------ replay batches (ring -> trainer inputs) */
 /* A training batch goes from the ring straight into the trainer's static inputs: one launch on `stream` reads the B
  * ring slots idx_dev names (int64 [B], repeats allowed), applies one of the eight board symmetries, widens the types
