@@ -183,30 +183,6 @@ def call(name, *args):
     return check(getattr(load(), name)(*[ptr(a) if isinstance(a, torch.Tensor) else a for a in args]))
 
 
-def replay_positions(rb, rows_host, rows_dev, P, board, player, last, count, stream=None):
-    """gmz_replay_positions on ``stream`` (default: the current one): rows 0..P-1 of the engine inputs ``board`` int8
-    [G, A], ``player`` int8 [G], ``last`` int32 [G], ``count`` int32 [G] decoded from the step-0 planes of the ring
-    slots the (slot, move count) table names (``rows_host`` pinned int32 [>= P, 2], ``rows_dev`` its device copy),
-    rows P..G-1 empty boards.  ``rb``: a device trainer.ReplayBuffer."""
-    c = rb.cfg
-    return call("gmz_replay_positions", int(c.BOARD_SIZE), int(c.NUM_UNROLL_STEPS), int(rb.N), rb.obs, nbytes(rb.obs),
-                rows_host, int(P), rows_dev, nbytes(rows_dev), int(player.shape[0]), board, nbytes(board), player,
-                nbytes(player), last, nbytes(last), count, nbytes(count), stream_ptr(stream))
-
-
-def replay_rewrite(rb, pol_new, val_new, P, jobs_host, jobs_dev, n_jobs, stream=None):
-    """gmz_replay_rewrite on ``stream`` (default: the current one): the staged search results ``pol_new`` f64 [>= P, A]
-    and ``val_new`` f32 [>= P] become the policy and n-step value targets of the ring slices of the ``n_jobs`` games in
-    the (slot, kept, n, drop, winner, first) table (``jobs_host`` pinned int32 [>= n_jobs, 6], ``jobs_dev`` its device
-    copy).  ``rb``: a device trainer.ReplayBuffer; discount, n-step and unroll from rb.cfg."""
-    c = rb.cfg
-    n_steps = int(c.N_STEPS)
-    pw = (ctypes.c_double * (n_steps + 1))(*[c.DISCOUNT ** i for i in range(n_steps + 1)])
-    return call("gmz_replay_rewrite", int(c.BOARD_SIZE), int(c.NUM_UNROLL_STEPS), n_steps, int(rb.N), rb.pol,
-                nbytes(rb.pol), rb.val, nbytes(rb.val), pol_new, nbytes(pol_new), val_new, nbytes(val_new), int(P),
-                jobs_host, int(n_jobs), jobs_dev, nbytes(jobs_dev), pw, stream_ptr(stream))
-
-
 _QUERIED = {}
 
 

@@ -1,10 +1,10 @@
 // gmz_replay.hip — finished self-play games from the device history (worker.GameHistory) straight into the trainer's
-// device replay ring (trainer.ReplayBuffer), one launch per self-play move; and, further down, training batches from
+// device replay ring (replay.ReplayBuffer), one launch per self-play move; and, further down, training batches from
 // that ring into the trainer's inputs (gmz_replay_gather) and the PER draw that picks them (gmz_replay_per_sample).
 // Between the two: the ring's own games as engine positions and their re-searched targets back into the ring
 // (gmz_replay_positions, gmz_replay_rewrite).
 //
-// Bit-exact restatement of records.final_rewards + records.compute_n_step_returns + loop.slices_from_game (built
+// Bit-exact restatement of records.final_rewards + records.compute_n_step_returns + replay.slices_from_game (built
 // with -ffp-contract=off): the ring holds what the host path would have uploaded, bit for bit.
 //   rewards        d = n-1-t: +1 when d mod 4 is 0 or 3, -1 otherwise (r[n-1] = 1, r[n-2] = -1, r[i] = -r[i+2]);
 //                  all zero for a draw; 0 past the game.
@@ -23,7 +23,7 @@
 
 namespace gmz {
 
-struct ReplayJob {  // include/gmz.h's job record; worker.py builds it as 8 int32
+struct ReplayJob {  // include/gmz.h's job record; replay.py builds it as 8 int32
   int32_t game, bank, row0, n, winner, drop, slot, first;
 };
 static_assert(sizeof(ReplayJob) == 32, "job record layout");
@@ -67,15 +67,20 @@ __device__ __forceinline__ float n_step_target(const ReplayPow &P, int n_steps, 
   return v;
 }
 
-__global__ __launch_bounds__(256) void k_replay_ingest(const ReplayArgs a, const ReplayPow P) {
-  const int b = (int)blockIdx.x;
-  // last job whose first kept slice is <= b
-  int lo = 0, hi = a.n_jobs - 1;
+// The job of workgroup b: the last record (ReplayJob or RewriteJob) whose first slice is <= b.
+template <typename Job>
+__device__ __forceinline__ Job job_of_block(const Job *jobs, int n_jobs, int b) {
+  int lo = 0, hi = n_jobs - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (a.jobs[mid].first <= b) lo = mid; else hi = mid - 1;
+    if (jobs[mid].first <= b) lo = mid; else hi = mid - 1;
   }
-  const ReplayJob j = a.jobs[lo];
+  return jobs[lo];
+}
+
+__global__ __launch_bounds__(256) void k_replay_ingest(const ReplayArgs a, const ReplayPow P) {
+  const int b = (int)blockIdx.x;
+  const ReplayJob j = job_of_block(a.jobs, a.n_jobs, b);
   const int kk = b - j.first;
   // the host validated the table it was given; a device copy that differs from it writes nothing
   if (j.game < 0 || j.game >= a.G || (j.bank != 0 && j.bank != 1) || j.row0 < 0 || j.n < 1 ||
@@ -186,13 +191,7 @@ struct RewriteArgs {
 
 __global__ __launch_bounds__(256) void k_replay_rewrite(const RewriteArgs a, const ReplayPow P) {
   const int b = (int)blockIdx.x;
-  // last job whose first surviving slice is <= b
-  int lo = 0, hi = a.n_jobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.jobs[mid].first <= b) lo = mid; else hi = mid - 1;
-  }
-  const RewriteJob j = a.jobs[lo];
+  const RewriteJob j = job_of_block(a.jobs, a.n_jobs, b);
   const int kk = b - j.first;
   // the host validated the table it was given; a device copy that differs from it writes nothing
   if (j.slot < 0 || j.slot >= a.N || j.kept < 1 || j.kept > a.N || j.n < 1 || j.drop < 0 || j.drop != j.n - j.kept ||
@@ -215,7 +214,7 @@ __global__ __launch_bounds__(256) void k_replay_rewrite(const RewriteArgs a, con
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// Training batches from the ring into the trainer's static inputs (trainer.ReplayBuffer.gather_into), one launch.
+// Training batches from the ring into the trainer's static inputs (replay.ReplayBuffer.gather_into), one launch.
 //
 // Bit-exact restatement of trainer.augment on batch = (obs[idx].float(), act[idx], rew[idx], pol[idx], val[idx]):
 //   planes, policies  torch.rot90(x, k) then torch.flip of the last axis when flip.  Destination cell (i, j) reads the
@@ -425,9 +424,40 @@ static inline void per_sizes(int count, long &ngroups, long &nchunks) {
 using namespace gmz;
 
 // host helpers of the entry points' validation
-static int short_capacity(const char *fn, const char *name, size_t have, size_t need) {
-  return fail(std::string(fn) + ": " + name + " of " + std::to_string(have) + " bytes is short of " +
-              std::to_string(need));
+static int below_one(const char *fn, const char *name, long v) {
+  return fail(std::string(fn) + ": " + name + " " + std::to_string(v) + " < 1");
+}
+
+// the slices' geometry, the checks every entry point that takes it opens with (one without n_steps passes 1)
+static int check_geometry(const char *fn, int board_size, int unroll, int n_steps = 1) {
+  if (board_size < 5 || board_size > 22)
+    return fail(std::string(fn) + ": board_size " + std::to_string(board_size) + " outside 5..22");
+  if (unroll < 1) return below_one(fn, "unroll", unroll);
+  if (n_steps < 1 || n_steps > GMZ_REPLAY_MAX_N_STEPS)
+    return fail(std::string(fn) + ": n_steps " + std::to_string(n_steps) + " outside 1.." +
+                std::to_string(GMZ_REPLAY_MAX_N_STEPS));
+  return 0;
+}
+
+struct Capacity {  // a buffer's size in bytes against what the call writes or reads; `need` as the refusal words it
+  const char *name;
+  size_t have, need;
+  std::string need_text;
+};
+
+// the first buffer of `caps` that is short, refused; 0 when every one holds its need
+static int check_capacities(const char *fn, std::initializer_list<Capacity> caps) {
+  for (const Capacity &c : caps)
+    if (c.have < c.need)
+      return fail(std::string(fn) + ": " + c.name + " of " + std::to_string(c.have) + " bytes is short of " +
+                  (c.need_text.empty() ? std::to_string(c.need) : c.need_text));
+  return 0;
+}
+
+static ReplayPow replay_pow(const double *discount_pow, int n_steps) {
+  ReplayPow P;
+  for (int i = 0; i <= GMZ_REPLAY_MAX_N_STEPS; ++i) P.pw[i] = i <= n_steps ? discount_pow[i] : 0.0;
+  return P;
 }
 
 // ring slot runs as linear [begin, end) ranges: a run of `len` slots from `slot` that passes the ring's end is two
@@ -452,12 +482,8 @@ GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G,
                                  float *ring_rew_dev, float *ring_pol_dev, float *ring_val_dev, float *ring_prio_dev,
                                  int N, const void *jobs_host, int n_jobs, const void *jobs_dev, size_t jobs_dev_bytes,
                                  const double *discount_pow, const float *priority_dev, void *stream) {
-  if (board_size < 5 || board_size > 22)
-    return fail("gmz_replay_ingest: board_size " + std::to_string(board_size) + " outside 5..22");
-  if (unroll < 1) return fail("gmz_replay_ingest: unroll " + std::to_string(unroll) + " < 1");
-  if (n_steps < 1 || n_steps > GMZ_REPLAY_MAX_N_STEPS)
-    return fail("gmz_replay_ingest: n_steps " + std::to_string(n_steps) + " outside 1.." +
-                std::to_string(GMZ_REPLAY_MAX_N_STEPS));
+  const char *fn = "gmz_replay_ingest";
+  if (check_geometry(fn, board_size, unroll, n_steps)) return -1;
   if (G < 1 || L < 1 || N < 1) return fail("gmz_replay_ingest: G, L and N must be positive");
   if (n_jobs < 0) return fail("gmz_replay_ingest: n_jobs < 0");
   if (n_jobs == 0) return 0;
@@ -465,9 +491,9 @@ GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G,
   if (!hist_board_dev || !hist_player_dev || !hist_last_dev || !hist_policy_dev || !hist_value_dev || !hist_action_dev ||
       !ring_obs_dev || !ring_act_dev || !ring_rew_dev || !ring_pol_dev || !ring_val_dev || !ring_prio_dev)
     return fail("gmz_replay_ingest: a history or ring pointer is NULL");
-  if (jobs_dev_bytes < (size_t)n_jobs * sizeof(ReplayJob))
-    return fail("gmz_replay_ingest: device job table of " + std::to_string(jobs_dev_bytes) + " bytes is short of " +
-                std::to_string(n_jobs) + " jobs x " + std::to_string(sizeof(ReplayJob)));
+  if (check_capacities(fn, {{"device job table", jobs_dev_bytes, (size_t)n_jobs * sizeof(ReplayJob),
+                             std::to_string(n_jobs) + " jobs x " + std::to_string(sizeof(ReplayJob))}}))
+    return -1;
   const ReplayJob *jobs = (const ReplayJob *)jobs_host;
   long total = 0;
   std::vector<std::pair<long, long>> spans;  // kept slices as linear [begin, end) ring ranges
@@ -502,9 +528,8 @@ GMZ_EXPORT int gmz_replay_ingest(int board_size, int unroll, int n_steps, int G,
   a.jobs = (const ReplayJob *)jobs_dev;
   a.prio = priority_dev;
   a.A = board_size * board_size; a.U = unroll; a.n_steps = n_steps; a.G = G; a.L = L; a.N = N; a.n_jobs = n_jobs;
-  ReplayPow P;
-  for (int i = 0; i <= GMZ_REPLAY_MAX_N_STEPS; ++i) P.pw[i] = i <= n_steps ? discount_pow[i] : 0.0;
-  hipLaunchKernelGGL(k_replay_ingest, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a, P);
+  hipLaunchKernelGGL(k_replay_ingest, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a,
+                     replay_pow(discount_pow, n_steps));
   GMZ_LAUNCH_CHECK();
   return 0;
 }
@@ -516,24 +541,21 @@ GMZ_EXPORT int gmz_replay_positions(int board_size, int unroll, int N, const uin
                                     size_t last_out_bytes, int32_t *count_out_dev, size_t count_out_bytes,
                                     void *stream) {
   const char *fn = "gmz_replay_positions";
-  if (board_size < 5 || board_size > 22)
-    return fail("gmz_replay_positions: board_size " + std::to_string(board_size) + " outside 5..22");
-  if (unroll < 1) return fail("gmz_replay_positions: unroll " + std::to_string(unroll) + " < 1");
-  if (N < 1) return fail("gmz_replay_positions: N " + std::to_string(N) + " < 1");
-  if (G < 1) return fail("gmz_replay_positions: G " + std::to_string(G) + " < 1");
+  if (check_geometry(fn, board_size, unroll)) return -1;
+  if (N < 1) return below_one(fn, "N", N);
+  if (G < 1) return below_one(fn, "G", G);
   if (P < 1 || P > G) return fail("gmz_replay_positions: P " + std::to_string(P) + " outside 1..G = " + std::to_string(G));
   if (!ring_obs_dev || !rows_host || !rows_dev) return fail("gmz_replay_positions: ring_obs_dev, rows_host or rows_dev is NULL");
   if (!board_out_dev || !player_out_dev || !last_out_dev || !count_out_dev)
     return fail("gmz_replay_positions: an output pointer is NULL");
   const size_t A = (size_t)board_size * board_size, ng = (size_t)G;
-  if (ring_obs_bytes < (size_t)N * (size_t)(unroll + 1) * 3 * A)
-    return short_capacity(fn, "ring_obs", ring_obs_bytes, (size_t)N * (size_t)(unroll + 1) * 3 * A);
-  if (rows_dev_bytes < (size_t)P * sizeof(PositionRow))
-    return short_capacity(fn, "device row table", rows_dev_bytes, (size_t)P * sizeof(PositionRow));
-  if (board_out_bytes < ng * A) return short_capacity(fn, "board_out", board_out_bytes, ng * A);
-  if (player_out_bytes < ng) return short_capacity(fn, "player_out", player_out_bytes, ng);
-  if (last_out_bytes < ng * 4) return short_capacity(fn, "last_out", last_out_bytes, ng * 4);
-  if (count_out_bytes < ng * 4) return short_capacity(fn, "count_out", count_out_bytes, ng * 4);
+  if (check_capacities(fn, {{"ring_obs", ring_obs_bytes, (size_t)N * (size_t)(unroll + 1) * 3 * A},
+                            {"device row table", rows_dev_bytes, (size_t)P * sizeof(PositionRow)},
+                            {"board_out", board_out_bytes, ng * A},
+                            {"player_out", player_out_bytes, ng},
+                            {"last_out", last_out_bytes, ng * 4},
+                            {"count_out", count_out_bytes, ng * 4}}))
+    return -1;
   const PositionRow *rows = (const PositionRow *)rows_host;
   for (int i = 0; i < P; ++i) {
     const std::string at = "gmz_replay_positions: row " + std::to_string(i) + ": ";
@@ -557,13 +579,8 @@ GMZ_EXPORT int gmz_replay_rewrite(int board_size, int unroll, int n_steps, int N
                                   size_t val_new_bytes, int P, const void *jobs_host, int n_jobs, const void *jobs_dev,
                                   size_t jobs_dev_bytes, const double *discount_pow, void *stream) {
   const char *fn = "gmz_replay_rewrite";
-  if (board_size < 5 || board_size > 22)
-    return fail("gmz_replay_rewrite: board_size " + std::to_string(board_size) + " outside 5..22");
-  if (unroll < 1) return fail("gmz_replay_rewrite: unroll " + std::to_string(unroll) + " < 1");
-  if (n_steps < 1 || n_steps > GMZ_REPLAY_MAX_N_STEPS)
-    return fail("gmz_replay_rewrite: n_steps " + std::to_string(n_steps) + " outside 1.." +
-                std::to_string(GMZ_REPLAY_MAX_N_STEPS));
-  if (N < 1) return fail("gmz_replay_rewrite: N " + std::to_string(N) + " < 1");
+  if (check_geometry(fn, board_size, unroll, n_steps)) return -1;
+  if (N < 1) return below_one(fn, "N", N);
   if (P < 0) return fail("gmz_replay_rewrite: P " + std::to_string(P) + " < 0");
   if (n_jobs < 0) return fail("gmz_replay_rewrite: n_jobs < 0");
   if (n_jobs == 0) return 0;
@@ -571,16 +588,12 @@ GMZ_EXPORT int gmz_replay_rewrite(int board_size, int unroll, int n_steps, int N
   if (!ring_pol_dev || !ring_val_dev || !pol_new_dev || !val_new_dev)
     return fail("gmz_replay_rewrite: a ring or staging pointer is NULL");
   const size_t A = (size_t)board_size * board_size, U1 = (size_t)unroll + 1;
-  if (ring_pol_bytes < (size_t)N * U1 * A * sizeof(float))
-    return short_capacity(fn, "ring_pol", ring_pol_bytes, (size_t)N * U1 * A * sizeof(float));
-  if (ring_val_bytes < (size_t)N * U1 * sizeof(float))
-    return short_capacity(fn, "ring_val", ring_val_bytes, (size_t)N * U1 * sizeof(float));
-  if (pol_new_bytes < (size_t)P * A * sizeof(double))
-    return short_capacity(fn, "pol_new", pol_new_bytes, (size_t)P * A * sizeof(double));
-  if (val_new_bytes < (size_t)P * sizeof(float))
-    return short_capacity(fn, "val_new", val_new_bytes, (size_t)P * sizeof(float));
-  if (jobs_dev_bytes < (size_t)n_jobs * sizeof(RewriteJob))
-    return short_capacity(fn, "device job table", jobs_dev_bytes, (size_t)n_jobs * sizeof(RewriteJob));
+  if (check_capacities(fn, {{"ring_pol", ring_pol_bytes, (size_t)N * U1 * A * sizeof(float)},
+                            {"ring_val", ring_val_bytes, (size_t)N * U1 * sizeof(float)},
+                            {"pol_new", pol_new_bytes, (size_t)P * A * sizeof(double)},
+                            {"val_new", val_new_bytes, (size_t)P * sizeof(float)},
+                            {"device job table", jobs_dev_bytes, (size_t)n_jobs * sizeof(RewriteJob)}}))
+    return -1;
   const RewriteJob *jobs = (const RewriteJob *)jobs_host;
   long total = 0;
   std::vector<std::pair<long, long>> spans;
@@ -608,9 +621,8 @@ GMZ_EXPORT int gmz_replay_rewrite(int board_size, int unroll, int n_steps, int N
   a.pol_new = pol_new_dev; a.val_new = val_new_dev; a.r_pol = ring_pol_dev; a.r_val = ring_val_dev;
   a.jobs = (const RewriteJob *)jobs_dev;
   a.A = (int)A; a.U = unroll; a.n_steps = n_steps; a.N = N; a.P = P; a.n_jobs = n_jobs;
-  ReplayPow pw;
-  for (int i = 0; i <= GMZ_REPLAY_MAX_N_STEPS; ++i) pw.pw[i] = i <= n_steps ? discount_pow[i] : 0.0;
-  hipLaunchKernelGGL(k_replay_rewrite, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a, pw);
+  hipLaunchKernelGGL(k_replay_rewrite, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a,
+                     replay_pow(discount_pow, n_steps));
   GMZ_LAUNCH_CHECK();
   return 0;
 }
@@ -622,11 +634,10 @@ GMZ_EXPORT int gmz_replay_gather(int board_size, int unroll, int N, int count, i
                                  float *rew_out_dev, size_t rew_out_bytes, float *pol_out_dev, size_t pol_out_bytes,
                                  float *val_out_dev, size_t val_out_bytes, int64_t *act_aug_out_dev,
                                  size_t act_aug_out_bytes, float *w_out_dev, size_t w_out_bytes, void *stream) {
-  if (board_size < 5 || board_size > 22)
-    return fail("gmz_replay_gather: board_size " + std::to_string(board_size) + " outside 5..22");
-  if (unroll < 1) return fail("gmz_replay_gather: unroll " + std::to_string(unroll) + " < 1");
-  if (B < 1) return fail("gmz_replay_gather: B " + std::to_string(B) + " < 1");
-  if (N < 1) return fail("gmz_replay_gather: N " + std::to_string(N) + " < 1");
+  const char *fn = "gmz_replay_gather";
+  if (check_geometry(fn, board_size, unroll)) return -1;
+  if (B < 1) return below_one(fn, "B", B);
+  if (N < 1) return below_one(fn, "N", N);
   if (count < 1 || count > N)
     return fail("gmz_replay_gather: count " + std::to_string(count) + " outside 1..N = " + std::to_string(N));
   if (k < 0 || k > 3) return fail("gmz_replay_gather: k " + std::to_string(k) + " outside 0..3");
@@ -639,19 +650,14 @@ GMZ_EXPORT int gmz_replay_gather(int board_size, int unroll, int N, int count, i
   const size_t A = (size_t)board_size * board_size, U = (size_t)unroll, nb = (size_t)B;
   if ((nb * (U + 1) > (size_t)0x7fffffff))
     return fail("gmz_replay_gather: B * (unroll + 1) = " + std::to_string(nb * (U + 1)) + " passes one launch's grid");
-  const struct { const char *name; size_t have, need; } caps[] = {
-      {"obs_out", obs_out_bytes, nb * (U + 1) * 3 * A * sizeof(float)},
-      {"act_out", act_out_bytes, nb * U * sizeof(int64_t)},
-      {"rew_out", rew_out_bytes, nb * U * sizeof(float)},
-      {"pol_out", pol_out_bytes, nb * (U + 1) * A * sizeof(float)},
-      {"val_out", val_out_bytes, nb * (U + 1) * sizeof(float)},
-      {"act_aug_out", act_aug_out_bytes, nb * U * sizeof(int64_t)},
-      {"w_out", w_out_bytes, nb * sizeof(float)},
-  };
-  for (const auto &c : caps)
-    if (c.have < c.need)
-      return fail(std::string("gmz_replay_gather: ") + c.name + " of " + std::to_string(c.have) +
-                  " bytes is short of " + std::to_string(c.need));
+  if (check_capacities(fn, {{"obs_out", obs_out_bytes, nb * (U + 1) * 3 * A * sizeof(float)},
+                            {"act_out", act_out_bytes, nb * U * sizeof(int64_t)},
+                            {"rew_out", rew_out_bytes, nb * U * sizeof(float)},
+                            {"pol_out", pol_out_bytes, nb * (U + 1) * A * sizeof(float)},
+                            {"val_out", val_out_bytes, nb * (U + 1) * sizeof(float)},
+                            {"act_aug_out", act_aug_out_bytes, nb * U * sizeof(int64_t)},
+                            {"w_out", w_out_bytes, nb * sizeof(float)}}))
+    return -1;
   GatherArgs a;
   a.r_obs = ring_obs_dev; a.r_act = ring_act_dev; a.r_rew = ring_rew_dev; a.r_pol = ring_pol_dev; a.r_val = ring_val_dev;
   a.idx = idx_dev; a.w = w_dev;
@@ -664,8 +670,9 @@ GMZ_EXPORT int gmz_replay_gather(int board_size, int unroll, int N, int count, i
 }
 
 GMZ_EXPORT int gmz_replay_per_sample_workspace_bytes(int count, int B, size_t *out) {
-  if (count < 1) return fail("gmz_replay_per_sample_workspace_bytes: count " + std::to_string(count) + " < 1");
-  if (B < 1) return fail("gmz_replay_per_sample_workspace_bytes: B " + std::to_string(B) + " < 1");
+  const char *fn = "gmz_replay_per_sample_workspace_bytes";
+  if (count < 1) return below_one(fn, "count", count);
+  if (B < 1) return below_one(fn, "B", B);
   if (!out) return fail("gmz_replay_per_sample_workspace_bytes: out is NULL");
   long ngroups, nchunks;
   per_sizes(count, ngroups, nchunks);
@@ -676,8 +683,9 @@ GMZ_EXPORT int gmz_replay_per_sample_workspace_bytes(int count, int B, size_t *o
 GMZ_EXPORT int gmz_replay_per_sample(const float *prio_dev, const double *r_dev, int count, int B, int64_t *idx_dev,
                                      size_t idx_bytes, double *prob_dev, size_t prob_bytes, void *workspace_dev,
                                      size_t ws_bytes, void *stream) {
-  if (count < 1) return fail("gmz_replay_per_sample: count " + std::to_string(count) + " < 1");
-  if (B < 1) return fail("gmz_replay_per_sample: B " + std::to_string(B) + " < 1");
+  const char *fn = "gmz_replay_per_sample";
+  if (count < 1) return below_one(fn, "count", count);
+  if (B < 1) return below_one(fn, "B", B);
   if (!prio_dev) return fail("gmz_replay_per_sample: prio_dev is NULL");
   if (!r_dev) return fail("gmz_replay_per_sample: r_dev is NULL");
   if (!idx_dev) return fail("gmz_replay_per_sample: idx_dev is NULL");
@@ -688,15 +696,11 @@ GMZ_EXPORT int gmz_replay_per_sample(const float *prio_dev, const double *r_dev,
   long ngroups, nchunks;
   per_sizes(count, ngroups, nchunks);
   const size_t need = (size_t)(ngroups + nchunks) * sizeof(double);
-  if (ws_bytes < need)
-    return fail("gmz_replay_per_sample: workspace of " + std::to_string(ws_bytes) + " bytes is short of " +
-                std::to_string(need) + " (gmz_replay_per_sample_workspace_bytes)");
-  if (idx_bytes < (size_t)B * sizeof(int64_t))
-    return fail("gmz_replay_per_sample: idx of " + std::to_string(idx_bytes) + " bytes is short of " +
-                std::to_string((size_t)B * sizeof(int64_t)));
-  if (prob_bytes < (size_t)B * sizeof(double))
-    return fail("gmz_replay_per_sample: prob of " + std::to_string(prob_bytes) + " bytes is short of " +
-                std::to_string((size_t)B * sizeof(double)));
+  if (check_capacities(fn, {{"workspace", ws_bytes, need,
+                             std::to_string(need) + " (gmz_replay_per_sample_workspace_bytes)"},
+                            {"idx", idx_bytes, (size_t)B * sizeof(int64_t)},
+                            {"prob", prob_bytes, (size_t)B * sizeof(double)}}))
+    return -1;
   double *l = (double *)workspace_dev, *T = l + ngroups;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_per_groups, dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, st, prio_dev, count, (int)nchunks,

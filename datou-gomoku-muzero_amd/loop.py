@@ -10,8 +10,8 @@ own share of the work, time-sliced on its GPU:
   self-play   G games on the HIP engine (engine.BatchedSelfPlayEngine + network.GomokuNetHip), the
               move history kept on the device and harvested one move behind (worker.GameHistory);
   replay      every finished game becomes the reference's TrainingSlices (records.py semantics,
-              built as arrays by ``slices_from_game``) appended to THIS rank's device-resident
-              replay shard (trainer.ReplayBuffer) — no data crosses ranks; ``device_ingest=True``: the
+              built as arrays by ``replay.slices_from_game``) appended to THIS rank's device-resident
+              replay shard (replay.ReplayBuffer) — no data crosses ranks; ``device_ingest=True``: the
               slices go from the device history into the shard by one HIP launch per move
               (gmz_replay_ingest, bit-identical; nothing but a job table crosses the bus);
               ``device_batches=True``: a training batch goes from the shard into the trainer's inputs by the
@@ -42,29 +42,8 @@ import time
 import numpy as np
 import torch
 
-from . import records as R
+from .replay import ReplayBuffer, slices_from_game
 from .weight_sync import broadcast_state_dict
-from .worker import board_states_to_obs
-
-
-def slices_from_game(boards, players, lasts, pols, vals, acts, winner, H, discount, n_steps, unroll):
-    """One finished game -> the reference's TrainingSlices as stacked arrays (workers.py:183-222,
-    same values as records.build_game_record's slice list):
-    obs uint8 [n, U+1, 3, H, H], act int32 [n, U], rew f32 [n, U], pol f32 [n, U+1, A], val f32 [n, U+1]."""
-    n, U = len(acts), unroll
-    A = H * H
-    obs = board_states_to_obs(np.asarray(boards).reshape(n, A), np.asarray(players), np.asarray(lasts), H)
-    rew = R.final_rewards(n, winner)
-    vt = np.asarray(R.compute_n_step_returns(rew.tolist(), list(vals), discount, n_steps), dtype=np.float32)
-    pad = lambda x, k, v=0: np.concatenate([x, np.full((k,) + x.shape[1:], v, dtype=x.dtype)])  # noqa: E731
-    win = lambda x, w: np.lib.stride_tricks.sliding_window_view(x, w, axis=0)[:n]  # noqa: E731
-    o = win(pad(obs.astype(np.uint8), U + 1), U + 1)           # [n, 3, H, H, U+1]
-    a = win(pad(np.asarray(acts, np.int32), U, -1), U)         # [n, U]
-    r = win(pad(rew.astype(np.float32), U), U)
-    p = win(pad(np.asarray(pols, np.float32).reshape(n, A), U + 1), U + 1)  # [n, A, U+1]
-    v = win(pad(vt, U + 1), U + 1)
-    return (np.ascontiguousarray(np.moveaxis(o, -1, 1)), np.ascontiguousarray(a), np.ascontiguousarray(r),
-            np.ascontiguousarray(np.moveaxis(p, -1, 1)), np.ascontiguousarray(v))
 
 
 class SelfPlay:
@@ -91,7 +70,7 @@ class SelfPlay:
 
     def ingest_into(self, buffer, stream=None):
         """Device hand-over: from now on ``step`` / ``flush`` write finished games straight into
-        ``buffer`` (trainer.ReplayBuffer.ingest_history, one HIP launch per move, on ``stream`` or the
+        ``buffer`` (replay.ReplayBuffer.ingest_history, one HIP launch per move, on ``stream`` or the
         current one) and return only their (game, winner, n_moves, missed_fives, missed_totals)."""
         self.ingest_buffer, self.ingest_stream = buffer, stream
 
@@ -161,10 +140,12 @@ class C4Loop:
         if self.ra is not None:
             self.ra.ring_stream = self.train_stream
         # device_ingest: finished games go from the self-play history to the shard in HIP (one launch per
-        # move, GameHistory.ingest) on the stream of every other ring operation; off = the host path
+        # move, ReplayBuffer.ingest_history) on the stream of every other ring operation; off = the host path
         self.device_ingest = bool(device_ingest)
         if self.device_ingest:
-            if not hasattr(getattr(selfplay, "hist", None), "ingest") or not hasattr(selfplay, "ingest_into"):
+            hist = getattr(selfplay, "hist", None)  # the ring reads its finished games and banks, and hands it an event
+            if not all(hasattr(hist, k) for k in ("finished", "after_ingest", "board")) \
+                    or not hasattr(selfplay, "ingest_into"):
                 raise ValueError("device_ingest needs a self-play source with a device history (loop.SelfPlay)")
             if self.device.type != "cuda":
                 raise ValueError("device_ingest needs the loop on a GPU")
@@ -178,8 +159,7 @@ class C4Loop:
         if self.device_batches:
             if self.device.type != "cuda":
                 raise ValueError("device_batches needs the loop on a GPU")
-            if buffer.obs.device.type != "cuda":
-                raise ValueError("device_batches needs a device-resident ReplayBuffer, not one on %s" % buffer.obs.device)
+            buffer.need_device("device_batches")
             if not hasattr(trainer, "step_from") or int(trainer.cfg.PHYSICAL_BATCH_SIZE) != self.B:
                 raise ValueError("device_batches: the trainer steps on its PHYSICAL_BATCH_SIZE, not on a batch of %d"
                                  % self.B)
@@ -317,7 +297,7 @@ def run_c4(args, rank, world, dist, backend, log=print):
                                    args.loop_openings, n_in_row=cfg.N_IN_ROW)
     sp = SelfPlay(cfg, args.loop_games, sd, seed=args.seed + 7919 * rank, precision=getattr(args, "precision", "fp16"),
                   openings=openings)
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = ReplayBuffer(tcfg, device="cuda")
     if args.loop_prefill:
         from .weights import synthetic_slices
         rb.add_arrays(*synthetic_slices(args.loop_prefill, args.size, tcfg.NUM_UNROLL_STEPS,

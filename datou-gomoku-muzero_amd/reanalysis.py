@@ -15,7 +15,7 @@ results are those of the reference's sequential searches with the same Gumbel no
 the oracle in tests/test_reanalysis_gpu.py).
 
 ``RingReanalyser`` is the same re-search for the composed loop (loop.C4Loop): its games are the ones in the
-trainer's device replay ring (trainer.ReplayBuffer.games), decoded from the ring's own planes and rewritten in
+trainer's device replay ring (replay.ReplayBuffer.games), decoded from the ring's own planes and rewritten in
 place by two HIP launches (gmz_replay_positions, gmz_replay_rewrite), so the batches the trainer draws carry
 targets of the current network.  The missed-win census stays with the database path.
 """
@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import records as R
+from .replay import RotatingTables, rewrite_jobs, ring_positions_host, ring_rows
 
 
 @dataclass
@@ -128,30 +129,8 @@ class Reanalyser:
         return out
 
 
-def ring_rows(entries, N):
-    """The (ring slot, move count) of every surviving slice of ``entries`` (trainer.RingGame) in staging order (game
-    after game, positions drop..n-1) -> int32 [P, 2]; the move count of position t is start + t."""
-    rows = [np.stack([(e.slot + np.arange(e.kept)) % N, e.start + e.drop + np.arange(e.kept)], 1) for e in entries]
-    return np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 2), np.int32)
-
-
-def ring_positions_host(rb, rows):
-    """The host's decode of ring slices into search positions (the twin of gmz_replay_positions): ``rows`` int32
-    [P, 2] of (slot, move count) -> boards int8 [P, S, S], players int8 [P] (+1 on even counts), last_moves int32 [P]
-    (-1: none), move_counts int32 [P], from the step-0 planes of ``rb.obs``."""
-    S = int(rb.cfg.BOARD_SIZE)
-    P = len(rows)
-    idx = torch.as_tensor(rows[:, 0].astype(np.int64)).to(rb.obs.device)
-    planes = rb.obs[idx, 0].cpu().numpy().reshape(P, 3, S * S)
-    mc = rows[:, 1].astype(np.int32)
-    players = np.where(mc % 2 == 0, 1, -1).astype(np.int8)
-    boards = (planes[:, 0] != 0) * players[:, None] - (planes[:, 1] != 0) * players[:, None]
-    last = np.where(planes[:, 2].any(1), planes[:, 2].argmax(1), -1).astype(np.int32)
-    return boards.astype(np.int8).reshape(P, S, S), players, last, mc
-
-
 class RingReanalyser:
-    """MuZero Reanalyse on the trainer's replay ring: the games the ring holds (trainer.ReplayBuffer.games) are
+    """MuZero Reanalyse on the trainer's replay ring: the games the ring holds (replay.ReplayBuffer.games) are
     searched again with the current network and their policy and n-step value targets rewritten in place.
 
     It owns a network (``state_dict``: network.GomokuNetHip; None: the engine's hash backend) and an engine of
@@ -164,7 +143,8 @@ class RingReanalyser:
     the current stream, events between the two.  The host never waits for the work a pass enqueues, nor for anything
     in front of it on either stream: the padding mask of a short chunk is built on the device
     (set_active_device), and the one host wait is for the table set of two passes back, an event long passed
-    (as GameHistory's job tables).  An explicit ``gumbel`` (tests) is a pageable upload per chunk and does block.
+    (replay.RotatingTables, as the ingest's job tables).  An explicit ``gumbel`` (tests) is a pageable upload per chunk
+    and does block.
     With the ring on the CPU (or ``host`` set) the same pass goes through the host (:meth:`pass_host`)."""
 
     def __init__(self, cfg, buffer, state_dict=None, num_games=256, max_positions=None, seed=0, precision="fp16"):
@@ -198,8 +178,7 @@ class RingReanalyser:
         self.last = torch.full((G,), -1, dtype=torch.int32, device=dev)
         self.count = torch.zeros(G, dtype=torch.int32, device=dev)
         self._row = torch.arange(G, device=dev)  # row < n: the active mask of a chunk of n positions, made on the device
-        self._tables = None     # pinned + device (row table, job table), rotating behind events
-        self._tk = 0
+        self._tables = None     # replay.RotatingTables of (row table, job table), built by the first device pass
         self._loaded = None     # the engine's last read of board/player/last/count (the next decode waits for it)
         self._rewritten = None  # the last rewrite's read of the staging (the next pass's copies wait for it)
 
@@ -219,21 +198,6 @@ class RingReanalyser:
             P += e.kept
         return take, P
 
-    def _job_tables(self):
-        """The next (pinned rows, device rows, pinned jobs, device jobs, event) of the rotation; waits until the
-        launches that last read this set have passed (two passes back: long passed)."""
-        if self._tables is None:
-            M, dev = self.max_positions, self.eng.device
-            self._tables = [[torch.zeros(M, 2, dtype=torch.int32).pin_memory(),
-                             torch.zeros(M, 2, dtype=torch.int32, device=dev),
-                             torch.zeros(M, 6, dtype=torch.int32).pin_memory(),
-                             torch.zeros(M, 6, dtype=torch.int32, device=dev), None] for _ in range(2)]
-        t = self._tables[self._tk & 1]
-        self._tk += 1
-        if t[4] is not None:
-            t[4].synchronize()
-        return t
-
     def pass_(self, step, age=None, gumbel=None):
         """One re-analysis pass at trainer step ``step``: the eligible games (version <= step - age; ``age`` None =
         cfg.REANALYSIS_AGE_THRESHOLD), oldest search first, as many as the staging holds, are searched position by
@@ -242,7 +206,6 @@ class RingReanalyser:
         noise).  Returns (games, positions)."""
         if self.host:
             return self.pass_host(step, age, gumbel)
-        from . import _lib as L
         take, P = self._take(step, age)
         if not take:
             return 0, 0
@@ -251,26 +214,21 @@ class RingReanalyser:
         cur = torch.cuda.current_stream(dev)
         rs = self.ring_stream if self.ring_stream is not None else cur
         two = rs != cur
-        rows = ring_rows(take, rb.N)
-        kept = np.array([e.kept for e in take], dtype=np.int64)
-        jobs = np.stack([[e.slot, e.kept, e.n, e.drop, e.winner, 0] for e in take]).astype(np.int32)
-        jobs[:, 5] = np.cumsum(kept) - kept
-        J = len(take)
-        tab = self._job_tables()
-        rows_pin, rows_dev, jobs_pin, jobs_dev = tab[:4]
-        rows_pin[:P] = torch.from_numpy(rows)
-        jobs_pin[:J] = torch.from_numpy(jobs)
+        rows, J = ring_rows(take, rb.N), len(take)
+        if self._tables is None:  # (row table, job table); the one host wait is for the set of two passes back
+            self._tables = RotatingTables(dev, (self.max_positions, 2), (self.max_positions, 6))
+        tab = self._tables.take()
         with torch.cuda.stream(rs):
-            rows_dev[:P].copy_(rows_pin[:P], non_blocking=True)
-            jobs_dev[:J].copy_(jobs_pin[:J], non_blocking=True)
+            rows_pin, rows_dev = tab.upload(0, rows)
+            jobs_pin, jobs_dev = tab.upload(1, rewrite_jobs(take))
         if two and self._rewritten is not None:
             cur.wait_event(self._rewritten)  # the staging is free again
         for lo in range(0, P, G):
             n = min(G, P - lo)
             if two and self._loaded is not None:
                 rs.wait_event(self._loaded)  # the engine has taken the previous chunk's positions
-            L.replay_positions(rb, rows_pin[lo:lo + n], rows_dev[lo:lo + n], n, self.board, self.player, self.last,
-                               self.count, stream=rs)
+            rb.decode_positions(rows_pin[lo:lo + n], rows_dev[lo:lo + n], n, self.board, self.player, self.last,
+                                self.count, stream=rs)
             if two:
                 ev = torch.cuda.Event()
                 ev.record(rs)
@@ -296,10 +254,10 @@ class RingReanalyser:
             ev = torch.cuda.Event()
             ev.record(cur)
             rs.wait_event(ev)
-        L.replay_rewrite(rb, self.pol_new, self.val_new, P, jobs_pin, jobs_dev, J, stream=rs)
+        rb.rewrite_games(self.pol_new, self.val_new, P, jobs_pin, jobs_dev, J, stream=rs)
         done = torch.cuda.Event()
         done.record(rs)
-        tab[4] = self._rewritten = done
+        tab.event = self._rewritten = done
         return self._stamp(take, P, step)
 
     def pass_host(self, step, age=None, gumbel=None):

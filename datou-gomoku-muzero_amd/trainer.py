@@ -2035,340 +2035,7 @@ def muzero_loss(model, target_model, batch, is_weights, cfg, k=None, flip=None, 
 
 
 # ------------------------------------------------------------------------------ replay
-class RingGame:
-    """One game with slices in a ReplayBuffer's ring (an entry of its game directory): ``slot`` the ring slot of its
-    oldest surviving slice (slice k of the survivors is at (slot + k) mod N), ``kept`` surviving slices, ``n`` moves
-    recorded (``drop`` = n - kept slices lost from the front), ``winner``, ``start`` stones on the board at its first
-    recorded position, ``version`` the trainer step at which its targets were last searched, ``seq`` append order."""
-    __slots__ = ("slot", "kept", "n", "winner", "start", "version", "seq")
-
-    def __init__(self, slot, kept, n, winner, start, version, seq):
-        self.slot, self.kept, self.n, self.winner = int(slot), int(kept), int(n), int(winner)
-        self.start, self.version, self.seq = int(start), int(version), int(seq)
-
-    @property
-    def drop(self):
-        return self.n - self.kept
-
-    def __repr__(self):
-        return "RingGame(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k in self.__slots__)
-
-
-class ReplayBuffer:
-    """Device-resident ring of TrainingSlices with the sampling of replay_buffer.py:44-106.
-
-    Slices live in HBM as observation planes uint8 [N, U+1, 3, H, W] (0/1 planes), actions int32,
-    rewards f32, policies f32 [N, U+1, A], values f32; priorities f32 [N].  Sampling: uniform
-    without replacement (ENABLE_PER off, the reference default) or stratified proportional PER
-    (segment i of the total priority, one uniform draw each; prefix sums + binary search give the
-    same leaf as the reference's sum-tree descent), IS weights (count * p / total)^-beta / max.
-
-    ``games`` is the host-side directory of the games whose slices the ring holds (RingGame, oldest first): made by
-    :meth:`ingest_history` and by :meth:`add_arrays` with ``game=``, trimmed by every append, read by re-analysis
-    (:meth:`eligible`, reanalysis.RingReanalyser).  Slices appended without it (:meth:`add`, synthetic prefill) have
-    no entry and are never re-analysed."""
-
-    def __init__(self, cfg, capacity=None, device="cuda"):
-        c = cfg
-        self.cfg, self.N = c, int(capacity or c.TRAIN_BUFFER_SIZE)
-        U, H, A = c.NUM_UNROLL_STEPS, c.BOARD_SIZE, c.BOARD_SIZE * c.BOARD_SIZE
-        d = torch.device(device)
-        self.obs = torch.zeros(self.N, U + 1, 3, H, H, dtype=torch.uint8, device=d)
-        self.act = torch.zeros(self.N, U, dtype=torch.int32, device=d)
-        self.rew = torch.zeros(self.N, U, dtype=torch.float32, device=d)
-        self.pol = torch.zeros(self.N, U + 1, A, dtype=torch.float32, device=d)
-        self.val = torch.zeros(self.N, U + 1, dtype=torch.float32, device=d)
-        self.prio = torch.zeros(self.N, dtype=torch.float32, device=d)
-        self.ptr, self.count, self.max_priority, self.device = 0, 0, 1.0, d
-        self._per_ws = None  # gmz_replay_per_sample's workspace (sample_indices(hip=True)), built at first use
-        self.games, self._seq = [], 0  # the game directory (RingGame, oldest first) and its append counter
-        self.step = 0  # the trainer step ingest_history stamps on new entries (the loop keeps it current)
-
-    def __len__(self):
-        return self.count
-
-    def add(self, slices):
-        """Append TrainingSlice-like objects (observation, action_history, reward_history,
-        policy_history, value_history)."""
-        n = len(slices)
-        if n == 0:
-            return
-        self._trim(n)
-        idx = (torch.arange(n) + self.ptr) % self.N
-        st = lambda f, dt: torch.from_numpy(np.stack([np.asarray(getattr(s, f)) for s in slices]).astype(dt))  # noqa: E731
-        self.obs[idx] = st("observation", np.uint8).to(self.device)
-        self.act[idx] = st("action_history", np.int32).to(self.device)
-        self.rew[idx] = st("reward_history", np.float32).to(self.device)
-        self.pol[idx] = st("policy_history", np.float32).to(self.device)
-        self.val[idx] = st("value_history", np.float32).to(self.device)
-        if self.cfg.ENABLE_PER:
-            self.prio[idx.to(self.device)] = torch.as_tensor(self.max_priority, dtype=torch.float32, device=self.device)
-        else:
-            self.prio[idx.to(self.device)] = 1.0
-        self.ptr = (self.ptr + n) % self.N
-        self.count = min(self.N, self.count + n)
-
-    def add_arrays(self, obs, act, rew, pol, val, game=None):
-        """Append n slices given as stacked arrays/tensors (obs [n,U+1,3,H,W] 0/1, act [n,U] int,
-        rew [n,U], pol [n,U+1,A], val [n,U+1]); same ring semantics as :meth:`add`.  ``game`` = (winner, start,
-        version): the slices are one whole game's, in move order (loop.slices_from_game), and it gets a directory
-        entry (RingGame); without it no entry is made."""
-        n = moves = int(obs.shape[0])
-        if n == 0:
-            return
-        if n > self.N:  # only the newest N survive the ring
-            obs, act, rew, pol, val = obs[-self.N:], act[-self.N:], rew[-self.N:], pol[-self.N:], val[-self.N:]
-            n = self.N
-        self._trim(n)
-        if game is not None:
-            self._note_game(self.ptr, n, moves, *game)
-        idx = ((torch.arange(n) + self.ptr) % self.N).to(self.device)
-        def dv(x, dt):
-            if isinstance(x, np.ndarray) and not x.flags.writeable:
-                x = np.array(x)  # torch.as_tensor warns on (and would alias) a read-only numpy array
-            return torch.as_tensor(x).to(self.device, dt)
-        self.obs[idx] = dv(obs, torch.uint8)
-        self.act[idx] = dv(act, torch.int32)
-        self.rew[idx] = dv(rew, torch.float32)
-        self.pol[idx] = dv(pol, torch.float32)
-        self.val[idx] = dv(val, torch.float32)
-        if self.cfg.ENABLE_PER:
-            self.prio[idx] = torch.as_tensor(self.max_priority, dtype=torch.float32, device=self.device)
-        else:
-            self.prio[idx] = 1.0
-        self.ptr = (self.ptr + n) % self.N
-        self.count = min(self.N, self.count + n)
-
-    # ---------------------------------------------------------------- game directory
-    def _trim(self, k):
-        """The directory before ``k`` slices are appended at ``ptr``: the slots they overwrite hold the oldest
-        slices of the oldest games (worker.replay_jobs), so those entries' slot, kept and drop advance, and an entry
-        with nothing left goes.  A trimmed game stays whole for re-analysis: its surviving slices t >= drop read
-        positions t..t+U and values t+N_STEPS only."""
-        N, k, gone = self.N, min(int(k), self.N), 0
-        for e in self.games:
-            d = (e.slot - self.ptr) % N  # the entry's oldest slice is the d-th slot the append writes
-            if d >= k:
-                break
-            over = min(k - d, e.kept)
-            e.slot, e.kept = (e.slot + over) % N, e.kept - over
-            if e.kept:
-                break
-            gone += 1
-        del self.games[:gone]
-
-    def _note_game(self, slot, kept, n, winner, start, version):
-        self.games.append(RingGame(slot, kept, n, winner, start, version, self._seq))
-        self._seq += 1
-
-    def note_jobs(self, jobs, appended, version=None):
-        """The directory's half of an ingest, before ``ptr`` moves: ``jobs`` is worker.replay_jobs' table (int32
-        [J, 8]: game, bank, row0, n, winner, drop, slot, first; a game's first recorded row is its ``start``) of
-        games that append ``appended`` slices in all at ``ptr``."""
-        self._trim(appended)
-        v = self.step if version is None else version
-        for (_, _, row0, n, winner, drop, slot, _) in np.asarray(jobs).reshape(-1, 8).tolist():
-            self._note_game(slot, n - drop, n, winner, row0, v)
-
-    def eligible(self, step, age):
-        """The games whose targets are at least ``age`` trainer steps old at ``step`` (version <= step - age), oldest
-        search first: ordered by (version, seq)."""
-        lim = int(step) - int(age)
-        return sorted((e for e in self.games if e.version <= lim), key=lambda e: (e.version, e.seq))
-
-    def rewrite_games_host(self, entries, pol_new, val_new):
-        """New search results into the ring slices of ``entries`` (RingGame, in staging order) on the host:
-        ``pol_new`` f64 [P, A] and ``val_new`` f32 [P] hold, game after game, the rows of positions drop..n-1.  Each
-        game's policy and n-step value targets are loop.slices_from_game's for the new policies and values (the
-        positions before ``drop`` reach no surviving slice), assigned to its ring rows by torch indexing; planes,
-        actions, rewards and priorities stay.  The reference of gmz_replay_rewrite, and the path of a ring on the
-        CPU."""
-        from .loop import slices_from_game
-        c = self.cfg
-        H, A = int(c.BOARD_SIZE), int(c.BOARD_SIZE) ** 2
-        pol_new = np.asarray(pol_new, dtype=np.float64).reshape(-1, A)
-        val_new = np.asarray(val_new, dtype=np.float32).reshape(-1)
-        first = 0
-        for e in entries:
-            n, drop = e.n, e.drop
-            pols, vals = np.zeros((n, A), np.float64), np.zeros(n, np.float32)
-            pols[drop:], vals[drop:] = pol_new[first:first + e.kept], val_new[first:first + e.kept]
-            _, _, _, p, v = slices_from_game(np.zeros((n, A), np.int8), np.ones(n, np.int8), np.full(n, -1, np.int32),
-                                             pols, vals, np.zeros(n, np.int32), e.winner, H, c.DISCOUNT, c.N_STEPS,
-                                             c.NUM_UNROLL_STEPS)
-            idx = ((torch.arange(e.kept) + e.slot) % self.N).to(self.device)
-            self.pol[idx] = torch.from_numpy(np.array(p[drop:])).to(self.device)  # (copies: the views may be read-only)
-            self.val[idx] = torch.from_numpy(np.array(v[drop:])).to(self.device)
-            first += e.kept
-
-    def admission_priority(self):
-        """The priority of newly added slices as a device f32 scalar, or None for 1.0 (PER off, or no
-        priority updated yet): what gmz_replay_ingest reads on the device, so nothing synchronises."""
-        m = self.max_priority
-        if not self.cfg.ENABLE_PER or (not torch.is_tensor(m) and float(m) == 1.0):
-            return None
-        if not (torch.is_tensor(m) and m.dtype == torch.float32 and m.device == self.obs.device):
-            m = self.max_priority = torch.as_tensor(m, dtype=torch.float32).to(self.obs.device)
-        return m
-
-    def ingest_history(self, hist, sn, games=None):
-        """The finished games of ``hist``'s snapshot ``sn`` (worker.GameHistory) appended on the device: their
-        slices go from the history's banks into this ring by one HIP launch (gmz_replay_ingest) on the
-        current stream, bit-identical to GameHistory.harvest + loop.slices_from_game + :meth:`add_arrays`
-        game by game.  Returns the per-game (game slot, winner, n_moves, missed_fives, missed_totals)."""
-        c = self.cfg
-        U, H = int(c.NUM_UNROLL_STEPS), int(c.BOARD_SIZE)
-        if self.obs.device.type != "cuda":
-            raise ValueError("ingest_history needs a device-resident ReplayBuffer, not one on %s" % self.obs.device)
-        if getattr(hist, "A", None) != H * H or tuple(self.obs.shape[1:]) != (U + 1, 3, H, H):
-            raise ValueError("history of %s actions does not fit a ring of %dx%d boards, %d unroll steps"
-                             % (getattr(hist, "A", None), H, H, U))
-        if U < 1 or self.N < 1:
-            raise ValueError("ring of %d slices, %d unroll steps: smaller than one slice" % (self.N, U))
-        if hist.board.device != self.obs.device:
-            raise ValueError("history on %s, ring on %s" % (hist.board.device, self.obs.device))
-        return hist.ingest(sn, self, games=games)  # (its job table makes the games' directory entries: note_jobs)
-
-    def sample(self, B, rng=np.random, dist=None):
-        """replay_buffer.py:58-94.  ``dist``: torch.distributed when this buffer is one rank's shard of
-        a data-parallel trainer (sharded PER): each rank samples its B slices from its
-        own shard (rank chosen uniformly, then proportional within the shard, so a slice's sampling
-        probability is p_i / (N * T_rank)); the IS weights use the GLOBAL slice count (one all-reduce
-        SUM) and are normalised by the max over the global batch (one all-reduce MAX).  With one rank
-        this is exactly the reference's (count * p_i / T)^-beta / max."""
-        if self.count < B:
-            return None
-        if self.cfg.ENABLE_PER:
-            # no host synchronisation: the reference's per-segment draws uniform(seg*i, seg*(i+1))
-            # = seg * (i + random_sample()) take B host uniforms; the total stays on the device
-            p = self.prio[: self.count].double()
-            cum = torch.cumsum(p, 0)
-            total = cum[-1]
-            r = torch.from_numpy(rng.random_sample(B)).to(self.device, non_blocking=True)
-            u = (torch.arange(B, device=self.device, dtype=torch.float64) + r) * (total / B)
-            idx = torch.searchsorted(cum, u).clamp_max(self.count - 1)
-            prob = p[idx] / total
-            count = float(self.count)
-            if dist is not None and dist.get_world_size() > 1:
-                count = _allreduce(torch.tensor([count], dtype=torch.float64, device=self.device), dist)
-                prob = prob / dist.get_world_size()
-            w = (count * prob) ** (-self.cfg.PER_BETA)
-            wmax = w.max()
-            if dist is not None and dist.get_world_size() > 1:
-                wmax = _allreduce(wmax.reshape(1), dist, max_op=True)[0]
-            w = (w / wmax).float()
-        else:
-            idx = torch.from_numpy(rng.choice(self.count, B, replace=False)).to(self.device)
-            w = torch.ones(B, device=self.device)
-        batch = (self.obs[idx].float(), self.act[idx], self.rew[idx], self.pol[idx], self.val[idx])
-        return batch, idx, w
-
-    def sample_indices(self, B, rng=np.random, dist=None, hip=False):
-        """The index and weight half of :meth:`sample` -> (idx int64 [B], w f32 [B]), or None when the ring holds
-        fewer than B slices.  It consumes ``rng`` exactly as ``sample`` does.  ``hip``: with PER on, the draw
-        (priorities' prefix sums, the search, the probabilities) is gmz_replay_per_sample on the current stream,
-        in the summation order include/gmz.h states; the IS weights and the sharded-PER all-reduces stay the lines
-        of ``sample``, fed with its probabilities.  With PER off both settings draw the same host permutation."""
-        if hip and self.obs.device.type != "cuda":
-            raise ValueError("sample_indices(hip=True) needs a device-resident ReplayBuffer, not one on %s"
-                             % self.obs.device)
-        if self.count < B:
-            return None
-        if not self.cfg.ENABLE_PER:
-            idx = torch.from_numpy(rng.choice(self.count, B, replace=False)).to(self.device)
-            return idx, torch.ones(B, device=self.device)
-        r = torch.from_numpy(rng.random_sample(B)).to(self.device, non_blocking=True)
-        if hip:
-            from . import _lib as _L
-            ws = self._per_ws
-            if ws is None:  # sized for a full ring: the need grows with count
-                need = _L.query("gmz_replay_per_sample_workspace_bytes", int(self.N), int(B))
-                ws = self._per_ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
-            idx = torch.empty(B, dtype=torch.int64, device=self.device)
-            prob = torch.empty(B, dtype=torch.float64, device=self.device)
-            _L.call("gmz_replay_per_sample", self.prio, r, int(self.count), int(B), idx, _L.nbytes(idx), prob,
-                    _L.nbytes(prob), ws, _L.nbytes(ws), _L.stream_ptr())
-        else:
-            p = self.prio[: self.count].double()
-            cum = torch.cumsum(p, 0)
-            total = cum[-1]
-            u = (torch.arange(B, device=self.device, dtype=torch.float64) + r) * (total / B)
-            idx = torch.searchsorted(cum, u).clamp_max(self.count - 1)
-            prob = p[idx] / total
-        count = float(self.count)
-        if dist is not None and dist.get_world_size() > 1:
-            count = _allreduce(torch.tensor([count], dtype=torch.float64, device=self.device), dist)
-            prob = prob / dist.get_world_size()
-        w = (count * prob) ** (-self.cfg.PER_BETA)
-        wmax = w.max()
-        if dist is not None and dist.get_world_size() > 1:
-            wmax = _allreduce(wmax.reshape(1), dist, max_op=True)[0]
-        return idx, (w / wmax).float()
-
-    def gather_into(self, dst, idx, w, k, flip):
-        """The batch of ring slots ``idx`` (int64 [B], repeats allowed) under the board symmetry (k quarter turns,
-        then the mirror when ``flip``) written into ``dst``, a 7-tuple shaped like Trainer._static (observations f32
-        [B, U+1, 3, H, H], actions int64 [B, U], rewards, policies [B, U+1, A], search values, augmented actions
-        int64, weights f32 [B]; ``w`` None = ones): one HIP launch (gmz_replay_gather) on the current stream,
-        bit-identical to Trainer._augment_into_static on the batch :meth:`sample` builds by torch indexing."""
-        from . import _lib as _L
-        c = self.cfg
-        U, H = int(c.NUM_UNROLL_STEPS), int(c.BOARD_SIZE)
-        A, dev = H * H, self.obs.device
-        if dev.type != "cuda":
-            raise ValueError("gather_into needs a device-resident ReplayBuffer, not one on %s" % dev)
-        if tuple(self.obs.shape[1:]) != (U + 1, 3, H, H):
-            raise ValueError("ring planes %s do not hold %d unroll steps of %dx%d boards" % (tuple(self.obs.shape), U, H, H))
-        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev \
-                or not idx.is_contiguous():
-            raise ValueError("idx must be a contiguous int64 vector on %s" % dev)
-        B = int(idx.shape[0])
-        if w is not None and (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (B,)
-                              or w.device != dev or not w.is_contiguous()):
-            raise ValueError("w must be None or a contiguous float32 vector of %d weights on %s" % (B, dev))
-        f32, i64 = torch.float32, torch.int64
-        want = (("observations", f32, (B, U + 1, 3, H, H)), ("actions", i64, (B, U)), ("rewards", f32, (B, U)),
-                ("policies", f32, (B, U + 1, A)), ("values", f32, (B, U + 1)), ("augmented actions", i64, (B, U)),
-                ("weights", f32, (B,)))
-        if len(dst) != len(want):
-            raise ValueError("dst holds %d tensors, not the trainer's %d static inputs" % (len(dst), len(want)))
-        for t, (name, dt, shape) in zip(dst, want):
-            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or t.device != dev \
-                    or not t.is_contiguous():
-                raise ValueError("dst %s: expected a contiguous %s tensor of shape %s on %s, got %s %s on %s" % (
-                    name, dt, shape, dev, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
-                    getattr(t, "device", None)))
-        if int(k) not in (0, 1, 2, 3):
-            raise ValueError("k = %r is not a number of quarter turns 0..3" % (k,))
-        sized = [x for t in dst for x in (t, _L.nbytes(t))]
-        _L.call("gmz_replay_gather", H, U, int(self.N), int(self.count), B, self.obs, self.act, self.rew, self.pol,
-                self.val, idx, w, int(k), int(bool(flip)), *sized, _L.stream_ptr())
-
-    def update_priorities(self, idx, td, dist=None):
-        """replay_buffer.py:96-101; with ``dist`` the running max priority (the priority of newly added
-        slices) is kept global by an all-reduce MAX, so every shard admits new slices alike."""
-        if not self.cfg.ENABLE_PER:
-            return
-        p = td.abs().to(self.device).float() + self.cfg.PER_EPSILON
-        m = torch.maximum(torch.as_tensor(self.max_priority, device=self.device, dtype=torch.float32), p.max())
-        if dist is not None and dist.get_world_size() > 1:
-            m = _allreduce(m.reshape(1), dist, max_op=True)[0]
-        self.max_priority = m  # device scalar
-        self.prio[idx] = p
-
-
-def _allreduce(t, dist, max_op=False):
-    """All-reduce a small tensor (SUM or MAX) on any backend: RCCL takes device tensors, gloo host
-    tensors.  Returns the reduced tensor on ``t``'s device."""
-    op = dist.ReduceOp.MAX if max_op else dist.ReduceOp.SUM
-    if dist.get_backend() == "gloo" and t.is_cuda:
-        h = t.cpu()
-        dist.all_reduce(h, op=op)
-        out = h.to(t.device)
-    else:
-        dist.all_reduce(t, op=op)
-        out = t
-    return out
+from .replay import ReplayBuffer, RingGame, static_input_spec  # noqa: E402,F401  (the ring lives in replay.py)
 
 
 # ------------------------------------------------------------------------------ trainer
@@ -2747,11 +2414,8 @@ class Trainer:
         if flip is None:
             flip = bool(np.random.choice([True, False]))
         if self._static is None:  # _augment_into_static's shapes and dtypes
-            B, U, H = int(c.PHYSICAL_BATCH_SIZE), int(c.NUM_UNROLL_STEPS), int(c.BOARD_SIZE)
-            f32, i64 = torch.float32, torch.int64
-            self._static = tuple(torch.empty(shape, dtype=dt, device=self.device) for dt, shape in (
-                (f32, (B, U + 1, 3, H, H)), (i64, (B, U)), (f32, (B, U)), (f32, (B, U + 1, H * H)), (f32, (B, U + 1)),
-                (i64, (B, U)), (f32, (B,))))
+            self._static = tuple(torch.empty(shape, dtype=dt, device=self.device)
+                                 for _, dt, shape in static_input_spec(c, int(c.PHYSICAL_BATCH_SIZE)))
         rb.gather_into(self._static, idx, w, k, flip)
         if self.graph and self.step_count >= self.graph_warmup:
             logs, td = self._graph_step()

@@ -53,34 +53,6 @@ def board_states_to_obs(boards, players, last_moves, H):
     return obs
 
 
-def replay_jobs(games, ptr, count, N):
-    """Job table of gmz_replay_ingest for ``games`` = [(slot, bank, row0, n_moves, winner), ...] appended in
-    this order to a ring of N slices at ``ptr`` holding ``count``: what ReplayBuffer.add_arrays does game by
-    game (a game longer than the ring keeps its newest N slices, written from ``ptr`` on), with every
-    slice that a later game of the same table would overwrite left out, so no two kept slices share a
-    ring slot.  Such slices are always the oldest of their game: a drop from the front.
-    Returns (jobs int32 [J, 8] = game, bank, row0, n, winner, drop, slot, first; new ptr; new count)."""
-    N, p = int(N), int(ptr)
-    starts = []
-    for (_, _, _, n, _) in games:
-        k = min(int(n), N)
-        starts.append(p)
-        p = (p + k) % N
-        count = min(N, int(count) + k)
-    rows, cover = [], 0  # cover: ring slots written by the games after this one, a run from this game's end on
-    for (g, bk, s0, n, w), st in zip(reversed(games), reversed(starts)):
-        k = min(int(n), N)
-        over = min(k, max(0, cover - (N - k)))
-        if k > over:
-            rows.append((g, bk, s0, n, w, n - k + over, (st + over) % N, 0))
-        cover = min(N, cover + k)
-    jobs = np.asarray(rows[::-1], dtype=np.int32).reshape(-1, 8)
-    if len(jobs):
-        kept = jobs[:, 3] - jobs[:, 5]
-        jobs[:, 7] = np.cumsum(kept) - kept
-    return jobs, p, count
-
-
 class GameHistory:
     """Per-game move history kept on the device, harvested one move behind (no per-move host sync).
 
@@ -92,10 +64,9 @@ class GameHistory:
     after the NEXT move has been queued) waits for that event — already passed by then — and copies
     each finished game's rows to the host with DMA copies on a side stream.  A bank is rewritten only
     when its slot's next game ends too, at least 2*N_IN_ROW-1 moves later, long after the harvest.
-    ``ingest`` is the harvest that never leaves the device: the finished games' TrainingSlices go from
-    the banks into a trainer.ReplayBuffer by one gmz_replay_ingest launch; only the job table (32 bytes
-    per game) crosses the bus.  ``record`` makes its stream wait for the last ingest launch, so a bank
-    is never rewritten before an ingest on another stream has read it."""
+    The harvest that never leaves the device is the ring's (replay.ReplayBuffer.ingest_history): it reads
+    ``finished`` and the banks, and hands the event of its launch to ``after_ingest``; ``record`` makes its
+    stream wait for it, so a bank is never rewritten before an ingest on another stream has read it."""
 
     def __init__(self, G, A, device, min_game_len=9):
         assert min_game_len >= 2, "a bank must survive one move after its game ended"
@@ -118,9 +89,11 @@ class GameHistory:
         pin = lambda dt: torch.zeros(G, dtype=dt).pin_memory()  # noqa: E731
         self.snaps = [dict(status=pin(torch.int8), mc=pin(torch.int32), bank=pin(torch.int64), mf=pin(torch.int32),
                            mt=pin(torch.int32), act=pin(torch.int32), ev=None) for _ in range(2)]
-        self._tables = None     # ingest: pinned + device job tables, rotating behind events
-        self._tk = 0
         self._ingest_ev = None  # the last ingest launch; the next record() waits for it on its stream
+
+    def after_ingest(self, event):
+        """``event`` follows a launch on another stream that reads the banks: the next ``record`` waits for it."""
+        self._ingest_ev = event
 
     def set_start(self, move_counts):
         """The current games start from positions with ``move_counts`` stones (before their first
@@ -187,7 +160,7 @@ class GameHistory:
         """The games that ended at snapshot ``sn`` (waits for its event), in slot order: list of (game slot,
         bank, first recorded row, n_moves, winner, missed_fives, missed_totals).  Abandoned games (action
         -1) are left out.  Every ended slot's bank restarts from row 0, so a snapshot is read once: by
-        ``harvest``, by ``ingest``, or by a caller that hands this list to both."""
+        ``harvest``, by the ring's ``ingest_history``, or by a caller that hands this list to both."""
         if sn is None or sn["ev"] is None:
             return []
         sn["ev"].synchronize()
@@ -205,59 +178,6 @@ class GameHistory:
                 continue
             out.append((int(g), bk, s0, int(mc[g]) + 1 - s0, int(st[g]), int(mf[g]), int(mt[g])))
         return out
-
-    def _job_tables(self):
-        """The next (pinned table, device table, event) of the rotation; waits until the launch that last read
-        this pair has passed (two launches back: long passed)."""
-        if self._tables is None:
-            self._tables = [[torch.zeros(self.G, 8, dtype=torch.int32).pin_memory(),
-                             torch.zeros(self.G, 8, dtype=torch.int32, device=self.dev), None] for _ in range(2)]
-        t = self._tables[self._tk & 1]
-        self._tk += 1
-        if t[2] is not None:
-            t[2].synchronize()
-        return t
-
-    def ingest(self, sn, rb, games=None):
-        """``harvest`` without the host: the TrainingSlices of the games that ended at snapshot ``sn`` are
-        written from the banks into ``rb`` (a device trainer.ReplayBuffer of this board size) by one
-        gmz_replay_ingest launch on the current stream, bit-identical to harvest + loop.slices_from_game
-        + ReplayBuffer.add_arrays game by game in slot order (discount, n-step and unroll from rb.cfg).
-        ``games``: ``finished(sn)`` when the caller has taken it already.  Returns the per-game
-        (game slot, winner, n_moves, missed_fives, missed_totals)."""
-        from ._lib import check, load, nbytes, ptr, stream_ptr
-        import ctypes
-        if games is None:
-            games = self.finished(sn)
-        if not games:
-            return []
-        c = rb.cfg
-        jobs, new_ptr, new_count = replay_jobs([x[:5] for x in games], rb.ptr, rb.count, rb.N)
-        J = len(jobs)
-        if J > self.G:
-            raise ValueError("%d finished games in one snapshot of %d slots" % (J, self.G))
-        if J:
-            stream = torch.cuda.current_stream(self.dev)
-            stream.wait_event(sn["ev"])  # the banks' rows were written before the snapshot
-            tab = self._job_tables()
-            pinned, dev = tab[0], tab[1]
-            pinned[:J] = torch.from_numpy(jobs)
-            dev[:J].copy_(pinned[:J], non_blocking=True)
-            n_steps = int(c.N_STEPS)
-            pw = (ctypes.c_double * (n_steps + 1))(*[c.DISCOUNT ** i for i in range(n_steps + 1)])
-            prio = rb.admission_priority()
-            check(load().gmz_replay_ingest(
-                int(c.BOARD_SIZE), int(c.NUM_UNROLL_STEPS), n_steps, self.G, self.L, ptr(self.board), ptr(self.player),
-                ptr(self.last), ptr(self.pol), ptr(self.val), ptr(self.act), ptr(rb.obs), ptr(rb.act), ptr(rb.rew),
-                ptr(rb.pol), ptr(rb.val), ptr(rb.prio), rb.N, ptr(pinned), J, ptr(dev), nbytes(dev), pw, ptr(prio),
-                stream_ptr(stream)))
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            tab[2] = self._ingest_ev = ev
-        # the ring's game directory (re-analysis): trimmed by what the games append, then one entry per job
-        rb.note_jobs(jobs, sum(min(int(x[3]), int(rb.N)) for x in games))
-        rb.ptr, rb.count = new_ptr, new_count
-        return [(g, w, n, mf, mt) for (g, _, _, n, w, mf, mt) in games]
 
 
 def gpu_selfplay_worker(worker_id, worker_mode, data_queue, log_status_queue, ui_queue, shutdown_event,

@@ -614,7 +614,7 @@ int gmz_head_conv1x1_backward(int dtype, const void *x_dev, long P, int C, const
 /* ------------------------------------------------------------------ replay ingest (worker.GameHistory -> ring) */
 /* Finished self-play games go from the device move history straight into the trainer's device replay ring: one
  * launch writes every kept TrainingSlice of every job, bit-identical to records.final_rewards +
- * records.compute_n_step_returns + loop.slices_from_game + ReplayBuffer.add_arrays on the host.
+ * records.compute_n_step_returns + replay.slices_from_game + ReplayBuffer.add_arrays on the host.
  * History (bank b, game g, row r): board int8 [2][G][L][A], player int8 [2][G][L], last int32 [2][G][L] (-1 = none),
  * policy f64 [2][G][L][A], value f32 [2][G][L], action int32 [2][G][L]; A = board_size^2, board_size 5..22.
  * Ring of N slices: obs u8 [N][U+1][3][A], act int32 [N][U], rew f32 [N][U], pol f32 [N][U+1][A], val f32 [N][U+1],

@@ -109,11 +109,11 @@ def test_trim_and_warmup_order(tmp_path):
 
 def test_replay_warmup_from_reference_database(ref_copy):
     """workers.py:388 warm-up: load_latest_samples -> the trainer's device replay buffer."""
-    from datou_gomoku_muzero_amd import trainer as T
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
     st = F.RecordStore(ref_copy)
     slices = st.load_latest_samples(1000)
     cfg = T.TrainConfig(BOARD_SIZE=6, TRAIN_BUFFER_SIZE=64)
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
     rb.add(slices)
     assert len(rb) == len(slices)
     assert np.array_equal(rb.act[:len(slices)].numpy(), np.stack([s.action_history for s in slices]))

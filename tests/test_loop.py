@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from datou_gomoku_muzero_amd import loop as LP
+from datou_gomoku_muzero_amd import replay as RP
+from datou_gomoku_muzero_amd import worker as WK
 from datou_gomoku_muzero_amd import records as R
 
 
@@ -40,8 +42,8 @@ def test_slices_from_game_equal_build_game_record(seed):
     rs = np.random.RandomState(seed)
     _, winner, n, _, _, boards, players, lasts, pols, vals, acts = _random_game(rs)
     H = 6
-    got = LP.slices_from_game(boards, players, lasts, pols, vals, acts, winner, H, 0.997, 10, 5)
-    obs = LP.board_states_to_obs(boards, players, lasts, H)
+    got = RP.slices_from_game(boards, players, lasts, pols, vals, acts, winner, H, 0.997, 10, 5)
+    obs = WK.board_states_to_obs(boards, players, lasts, H)
     _, slices = R.build_game_record(list(obs), [int(a) for a in acts], list(pols), list(vals),
                                     list(boards.reshape(n, H, H)), winner, 0.997, 10, 5)
     want = [np.stack([getattr(s, f) for s in slices]) for f in
@@ -75,7 +77,7 @@ def _loop_rank(rank, port, q):
     cfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, NUM_FILTERS=16, PHYSICAL_BATCH_SIZE=8,
                         TRAIN_BUFFER_SIZE=4096, ENABLE_PER=True)
     tr = T.Trainer(cfg, device="cpu")
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
     sp = _ScriptedSelfPlay(100 + rank)  # different games per rank
     lp = LP.C4Loop(sp, tr, rb, cfg, 8, dist=dist, moves_per_iter=2, train_steps_per_iter=2, model_update_interval=3,
                    seed=7, device="cpu")
@@ -122,7 +124,7 @@ def _per_rank(rank, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=2)
     cfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, NUM_FILTERS=16, TRAIN_BUFFER_SIZE=64, ENABLE_PER=True,
                         PER_BETA=0.4)
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
     n = 20 + 12 * rank  # shards of different sizes and priorities
     from datou_gomoku_muzero_amd.weights import synthetic_slices
     rb.add_arrays(*synthetic_slices(n, 6, 5, np.random.RandomState(rank)))

@@ -36,7 +36,7 @@ def test_selfplay_records_train_and_hot_swap(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from datou_gomoku_muzero_amd import formats as F
-    from datou_gomoku_muzero_amd import trainer as T
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
     from datou_gomoku_muzero_amd import weights as W
     from datou_gomoku_muzero_amd.config import GmzConfig
     from datou_gomoku_muzero_amd.worker import gpu_selfplay_worker
@@ -55,7 +55,7 @@ def test_selfplay_records_train_and_hot_swap(tmp_path):
     n = sum(len(s) for _, s, _ in items)
     assert st.get_buffer_size() == n
     tc = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=8, TRAIN_BUFFER_SIZE=4096)
-    rb = T.ReplayBuffer(tc, device="cuda")
+    rb = RP.ReplayBuffer(tc, device="cuda")
     rb.add(st.load_latest_samples(n))
     st.close()
     assert len(rb) == n
@@ -121,13 +121,13 @@ def test_c4_loop_on_the_gpu_pushes_trained_weights_into_self_play():
     """loop.C4Loop with the real HIP self-play (single rank): finished games fill the replay shard,
     the trainer steps, and every push hot-swaps exactly the trainer's weights into the engine's
     network (its packed tensors equal a fresh packing of the trainer's state_dict)."""
-    from datou_gomoku_muzero_amd import loop as LP, network as N, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, network as N, replay as RP, trainer as T
     from datou_gomoku_muzero_amd.config import GmzConfig
     cfg = GmzConfig(BOARD_SIZE=6, NUM_SIMULATIONS=16, NUM_RES_BLOCKS=1)
     tcfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=16, TRAIN_BUFFER_SIZE=4096, ENABLE_PER=True)
     tr = T.Trainer(tcfg, device="cuda", graph=False)
     sp = LP.SelfPlay(cfg, 32, tr.state_dict_cpu(), seed=3)
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = RP.ReplayBuffer(tcfg, device="cuda")
     lp = LP.C4Loop(sp, tr, rb, tcfg, 16, moves_per_iter=2, train_steps_per_iter=1, model_update_interval=2)
     st = lp.run(40)
     torch.cuda.synchronize()
@@ -145,13 +145,13 @@ def test_c4_loop_concurrent_stream_trains_and_pushes():
     beside the self-play moves; the counts, the shard contents and the pushed weights are those of a
     consistent loop (every finished game's slices in the shard, pushes = steps / interval, the last
     push = the trainer's current weights)."""
-    from datou_gomoku_muzero_amd import loop as LP, network as N, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, network as N, replay as RP, trainer as T
     from datou_gomoku_muzero_amd.config import GmzConfig
     cfg = GmzConfig(BOARD_SIZE=6, NUM_SIMULATIONS=16, NUM_RES_BLOCKS=1)
     tcfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=16, TRAIN_BUFFER_SIZE=4096, ENABLE_PER=True)
     tr = T.Trainer(tcfg, device="cuda")
     sp = LP.SelfPlay(cfg, 32, tr.state_dict_cpu(), seed=3)
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = RP.ReplayBuffer(tcfg, device="cuda")
     lp = LP.C4Loop(sp, tr, rb, tcfg, 16, moves_per_iter=2, train_steps_per_iter=1, model_update_interval=2,
                    concurrent=True)
     assert lp.concurrent and lp.train_stream is not None
@@ -178,14 +178,14 @@ def test_c4_loop_at_its_own_workload(concurrent):
     run them: every finished game's slices reach the replay shard; the trainer samples those slices;
     every push hot-swaps exactly the trainer's weights into the self-play network; and (concurrent:
     trainer on its own HIP stream beside the moves) the same holds with the push on the trainer's stream."""
-    from datou_gomoku_muzero_amd import loop as LP, network as N, trainer as T, weights as W
+    from datou_gomoku_muzero_amd import loop as LP, network as N, replay as RP, trainer as T, weights as W
     from datou_gomoku_muzero_amd.config import GmzConfig
     cfg = GmzConfig(BOARD_SIZE=15, NUM_SIMULATIONS=32, NUM_RES_BLOCKS=8)
     tcfg = T.TrainConfig(BOARD_SIZE=15, NUM_RES_BLOCKS=8, PHYSICAL_BATCH_SIZE=360, TRAIN_BUFFER_SIZE=65536,
                          ENABLE_PER=True)
     tr = T.Trainer(tcfg, device="cuda")
     sp = LP.SelfPlay(cfg, 128, tr.state_dict_cpu(), seed=3, streams=1)
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = RP.ReplayBuffer(tcfg, device="cuda")
     prefill = 512
     rb.add_arrays(*W.synthetic_slices(prefill, 15, tcfg.NUM_UNROLL_STEPS, np.random.RandomState(0)))
     sampled = []
@@ -223,7 +223,7 @@ def test_c2_at_8192_games_and_the_c4_trainer_share_one_card():
     shard) resident on one MI355X together: one self-play move of every game and trainer steps run, and
     the card's used memory stays well inside its 288 GB (the hidden pool alone was 190 GB at 402 slots
     per game before round 4)."""
-    from datou_gomoku_muzero_amd import engine as E, loop as LP, trainer as T, weights as W
+    from datou_gomoku_muzero_amd import engine as E, loop as LP, replay as RP, trainer as T, weights as W
     from datou_gomoku_muzero_amd.config import GmzConfig
     free0, total = torch.cuda.mem_get_info()
     G = 8192
@@ -234,7 +234,7 @@ def test_c2_at_8192_games_and_the_c4_trainer_share_one_card():
     sp = LP.SelfPlay(cfg, G, tr.state_dict_cpu(), seed=3)
     pool_gb = sp.net.pool.numel() * 2 / 2 ** 30
     assert sp.net.pool.numel() == E.hidden_slots(cfg, G) * 225 * 128 and pool_gb < 50
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = RP.ReplayBuffer(tcfg, device="cuda")
     rb.add_arrays(*W.synthetic_slices(2048, 15, tcfg.NUM_UNROLL_STEPS, np.random.RandomState(0)))
     rs = np.random.RandomState(1)
     for _ in range(2):

@@ -5,7 +5,7 @@ gloo (tests/test_loop.py, test_trainer.py, test_pipeline_gpu.py) and RCCL itself
 8-GPU node.  This test runs the RCCL calls the product makes, on real device tensors, with one rank:
   * the weight push (weight_sync.broadcast_state_dict, workers.py:587-593's ModelWeightsUpdate);
   * the small SUM / MAX all-reduces of the sharded PER and of the bench's max-over-ranks timing
-    (trainer._allreduce, bench.collective_max);
+    (replay._allreduce, bench.collective_max);
   * the DDP trainer (trainer.Trainer under an initialised process group: rank 0's weights broadcast at
     construction, then per step the two gradient buckets' all-reduces captured inside the step's HIP
     graph, timed by the in-graph communication clock; and the fallback with the all-reduces between three
@@ -29,7 +29,7 @@ SCRIPT = textwrap.dedent(r"""
     import torch.distributed as dist
     torch.backends.cudnn.deterministic = True
     torch.cuda.set_device(0)
-    from datou_gomoku_muzero_amd import trainer as T, weights as W
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T, weights as W
     from datou_gomoku_muzero_amd.weight_sync import broadcast_state_dict
     import bench
 
@@ -75,8 +75,8 @@ SCRIPT = textwrap.dedent(r"""
         assert np.array_equal(out[k].cpu().numpy(), np.asarray(sd[k], dtype=np.float32)), k
     # PER / timing all-reduces on device tensors
     t = torch.tensor([3.5], device="cuda")
-    assert float(T._allreduce(t.clone(), dist)[0]) == 3.5
-    assert float(T._allreduce(t.clone(), dist, max_op=True)[0]) == 3.5
+    assert float(RP._allreduce(t.clone(), dist)[0]) == 3.5
+    assert float(RP._allreduce(t.clone(), dist, max_op=True)[0]) == 3.5
     assert bench.collective_max(2.25, dist, "nccl") == 2.25 and bench.collective_sum(2.0, dist, "nccl") == 2.0
     dist.barrier()
     dist.destroy_process_group()

@@ -83,10 +83,10 @@ def test_per_sample_refuses_every_bad_argument_before_launching():
 
 
 def _ring(count, prio, per=True, N=None):
-    from datou_gomoku_muzero_amd import trainer as T
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
     cfg = T.TrainConfig(BOARD_SIZE=5, NUM_UNROLL_STEPS=1, PHYSICAL_BATCH_SIZE=8, TRAIN_BUFFER_SIZE=N or count,
                         ENABLE_PER=per)
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
     rb.count = count
     rb.prio[:count] = torch.from_numpy(np.asarray(prio, np.float32))
     return rb
@@ -140,7 +140,7 @@ def test_sample_indices_is_the_index_and_weight_half_of_sample(per):
 
 
 def test_hip_paths_refuse_a_cpu_ring():
-    from datou_gomoku_muzero_amd import loop as LP, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, replay as RP, trainer as T
     rb = _ring(50, np.ones(50))
     with pytest.raises(ValueError, match="device-resident"):
         rb.sample_indices(8, np.random.RandomState(0), hip=True)
@@ -154,4 +154,4 @@ def test_hip_paths_refuse_a_cpu_ring():
     with pytest.raises(ValueError, match="device_batches needs the loop on a GPU"):
         LP.C4Loop(_Scripted(), None, rb, rb.cfg, 8, device="cpu", device_batches=True)
     assert LP.C4Loop(_Scripted(), None, rb, rb.cfg, 8, device="cpu").device_batches is False  # the default stays
-    assert T.ReplayBuffer.sample_indices.__defaults__[-1] is False
+    assert RP.ReplayBuffer.sample_indices.__defaults__[-1] is False

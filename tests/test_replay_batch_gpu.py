@@ -15,9 +15,9 @@ pytestmark = pytest.mark.gpu
 def _ring(H, U, N=37, count=23, per=True, seed=0, scramble=True):
     """A device ring of ``count`` synthetic slices; ``scramble``: random 0/1 planes, random f32 policies and some
     actions of -1, so that no board symmetry maps the data onto itself."""
-    from datou_gomoku_muzero_amd import trainer as T, weights as W
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T, weights as W
     cfg = T.TrainConfig(BOARD_SIZE=H, NUM_UNROLL_STEPS=U, PHYSICAL_BATCH_SIZE=7, TRAIN_BUFFER_SIZE=N, ENABLE_PER=per)
-    rb = T.ReplayBuffer(cfg, device="cuda")
+    rb = RP.ReplayBuffer(cfg, device="cuda")
     rs = np.random.RandomState(seed)
     rb.add_arrays(*W.synthetic_slices(count, H, U, rs))
     if scramble:
@@ -103,8 +103,8 @@ def test_gather_into_refuses_mismatches():
             rb.gather_into(good[:i] + (bad,) + good[i + 1:], idx, None, 0, False)
     with pytest.raises(ValueError, match="quarter turns"):
         rb.gather_into(good, idx, None, 4, False)
-    from datou_gomoku_muzero_amd import trainer as T
-    empty = T.ReplayBuffer(rb.cfg, device="cuda")
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
+    empty = RP.ReplayBuffer(rb.cfg, device="cuda")
     with pytest.raises(L.GmzError, match="count"):  # the library's own refusal: nothing to read yet
         empty.gather_into(good, idx, None, 0, False)
 
@@ -146,9 +146,9 @@ def test_per_draw_equals_the_stated_order_and_is_deterministic(count):
 def test_per_draw_equals_sample_where_every_sum_is_exact(count):
     """The dyadic priorities of tests/test_replay_batch.py on a device ring: sample_indices(hip=True) and sample with
     the same seed give the same idx and the same weights, bit for bit."""
-    from datou_gomoku_muzero_amd import trainer as T
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
     cfg = T.TrainConfig(BOARD_SIZE=5, NUM_UNROLL_STEPS=1, TRAIN_BUFFER_SIZE=count + 11, ENABLE_PER=True)
-    rb = T.ReplayBuffer(cfg, device="cuda")
+    rb = RP.ReplayBuffer(cfg, device="cuda")
     rb.count = count
     rb.prio[:count] = torch.from_numpy(REF.dyadic_priorities(count, np.random.RandomState(count))).cuda()
     for B in (1, 7, 360):
@@ -173,13 +173,13 @@ def _state_dict(cfg, seed):
 
 
 def _trainer_and_ring(per, seed=0, H=9, B=16, blocks=2, warmup=2):
-    from datou_gomoku_muzero_amd import trainer as T, weights as W
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T, weights as W
     cfg = T.TrainConfig(BOARD_SIZE=H, NUM_RES_BLOCKS=blocks, PHYSICAL_BATCH_SIZE=B, TRAIN_BUFFER_SIZE=200,
                         ENABLE_PER=per, LEARNING_RATE=1e-3)
     sd = _state_dict(cfg, 5)
     torch.manual_seed(seed)
     tr = T.Trainer(cfg, device="cuda", state_dict=sd, graph_warmup=warmup)
-    rb = T.ReplayBuffer(cfg, device="cuda")
+    rb = RP.ReplayBuffer(cfg, device="cuda")
     rb.add_arrays(*W.synthetic_slices(150, H, cfg.NUM_UNROLL_STEPS, np.random.RandomState(9)))
     if per:  # unequal priorities from the start
         rb.prio[:150] = torch.from_numpy(np.random.RandomState(2).uniform(0.05, 2.0, 150).astype(np.float32)).cuda()
@@ -256,7 +256,7 @@ def test_c4_loop_with_device_batches_equals_the_default():
     """C4Loop(device_batches=True) beside the default on test_loop.py's scripted self-play source, PER off (both
     paths draw the same host permutation): identical stats and trainer parameters; and the construction errors."""
     from test_loop import _ScriptedSelfPlay
-    from datou_gomoku_muzero_amd import loop as LP, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, replay as RP, trainer as T
     cfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=8, TRAIN_BUFFER_SIZE=512, ENABLE_PER=False)
     sd = _state_dict(cfg, 3)
     runs = []
@@ -264,7 +264,7 @@ def test_c4_loop_with_device_batches_equals_the_default():
         torch.manual_seed(0)
         np.random.seed(5)
         tr = T.Trainer(cfg, device="cuda", state_dict=sd, graph_warmup=2)
-        rb = T.ReplayBuffer(cfg, device="cuda")
+        rb = RP.ReplayBuffer(cfg, device="cuda")
         lp = LP.C4Loop(_ScriptedSelfPlay(100), tr, rb, cfg, 8, moves_per_iter=2, train_steps_per_iter=1,
                        model_update_interval=3, seed=7, device_batches=dev_batches)
         assert lp.device_batches is dev_batches
@@ -274,7 +274,7 @@ def test_c4_loop_with_device_batches_equals_the_default():
     (s0, p0, l0), (s1, p1, l1) = runs
     assert s0 == s1 and s0["train_steps"] >= 4 and s0["weight_pushes"] >= 1
     assert all(torch.equal(x, y) for x, y in zip(p0, p1)) and torch.equal(l0, l1)
-    cpu_rb = T.ReplayBuffer(cfg, device="cpu")
+    cpu_rb = RP.ReplayBuffer(cfg, device="cpu")
     with pytest.raises(ValueError, match="device-resident"):
         LP.C4Loop(_ScriptedSelfPlay(1), tr, cpu_rb, cfg, 8, device_batches=True)
     with pytest.raises(ValueError, match="PHYSICAL_BATCH_SIZE"):

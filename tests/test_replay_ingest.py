@@ -75,7 +75,7 @@ def _simulate(games, ptr, count, N):
     ("exactly the ring", 16, 5, 2, [16, 3]),
 ])
 def test_job_table_equals_sequential_add_arrays(name, N, ptr, count, lens):
-    from datou_gomoku_muzero_amd.worker import replay_jobs
+    from datou_gomoku_muzero_amd.replay import replay_jobs
     games = [(10 + j, j & 1, 3 * (j % 2), n, (-1, 0, 1)[j % 3]) for j, n in enumerate(lens)]
     jobs, new_ptr, new_count = replay_jobs(games, ptr, count, N)
     owner, want_ptr, want_count = _simulate(lens, ptr, count, N)
@@ -96,7 +96,7 @@ def test_job_table_equals_sequential_add_arrays(name, N, ptr, count, lens):
 
 
 def test_job_table_of_nothing_changes_nothing():
-    from datou_gomoku_muzero_amd.worker import replay_jobs
+    from datou_gomoku_muzero_amd.replay import replay_jobs
     jobs, ptr, count = replay_jobs([], 7, 9, 20)
     assert jobs.shape == (0, 8) and (ptr, count) == (7, 9)
 
@@ -104,7 +104,8 @@ def test_job_table_of_nothing_changes_nothing():
 def test_abandoned_game_contributes_nothing():
     """GameHistory.finished leaves an abandoned game (action -1) out, so it never reaches the table; its bank's
     start row is reset all the same.  Checked on the class without its device tensors."""
-    from datou_gomoku_muzero_amd.worker import GameHistory, replay_jobs
+    from datou_gomoku_muzero_amd.replay import replay_jobs
+    from datou_gomoku_muzero_amd.worker import GameHistory
 
     class _Ev:
         def synchronize(self):
@@ -162,9 +163,9 @@ def test_n_step_model_equals_compute_n_step_returns_bit_for_bit():
 
 
 def test_device_ingest_needs_a_device_history_and_a_device_ring():
-    from datou_gomoku_muzero_amd import loop as LP, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, replay as RP, trainer as T
     cfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=8, TRAIN_BUFFER_SIZE=64)
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
 
     class _Scripted:  # a self-play source without a device history, as tests/test_loop.py's stand-in
         moves = 0

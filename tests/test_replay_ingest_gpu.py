@@ -1,5 +1,5 @@
 """Finished games go from the device history to the replay ring in HIP (gmz_replay_ingest): the ring must hold,
-bit for bit, what GameHistory.harvest + loop.slices_from_game + ReplayBuffer.add_arrays put there."""
+bit for bit, what GameHistory.harvest + replay.slices_from_game + ReplayBuffer.add_arrays put there."""
 import numpy as np
 import pytest
 
@@ -50,7 +50,7 @@ def _snapshot(h, games):
 
 def _both_paths(h, sn, rb_host, rb_dev):
     """One snapshot's finished games through the host path into ``rb_host`` and the device path into ``rb_dev``."""
-    from datou_gomoku_muzero_amd.loop import slices_from_game
+    from datou_gomoku_muzero_amd.replay import slices_from_game
     c = rb_host.cfg
     fin = h.finished(sn)
     done = h.harvest(sn, games=fin)
@@ -72,10 +72,10 @@ def _assert_rings_equal(a, b):
 
 
 def _rings(H, n_steps, N, per):
-    from datou_gomoku_muzero_amd import trainer as T
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
     out = []
     for _ in range(2):
-        rb = T.ReplayBuffer(_tcfg(H, n_steps, N, per), device="cuda")
+        rb = RP.ReplayBuffer(_tcfg(H, n_steps, N, per), device="cuda")
         if per:  # the admission priority after an update_priorities: a device scalar
             rb.max_priority = torch.tensor(2.5, dtype=torch.float32, device="cuda")
         if N == 37:  # a full ring whose pointer is about to wrap
@@ -151,13 +151,13 @@ def test_c4_loop_with_device_ingest(concurrent):
     """loop.C4Loop(device_ingest=True) at the shapes of test_pipeline_gpu.py's loop tests, time-sliced and with the
     trainer on its own stream: every finished game's slices are in the shard, the trainer steps, the pushes follow
     the steps, and the engine reports no error."""
-    from datou_gomoku_muzero_amd import loop as LP, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, replay as RP, trainer as T
     from datou_gomoku_muzero_amd.config import GmzConfig
     cfg = GmzConfig(BOARD_SIZE=6, NUM_SIMULATIONS=16, NUM_RES_BLOCKS=1)
     tcfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=16, TRAIN_BUFFER_SIZE=4096, ENABLE_PER=True)
     tr = T.Trainer(tcfg, device="cuda") if concurrent else T.Trainer(tcfg, device="cuda", graph=False)
     sp = LP.SelfPlay(cfg, 32, tr.state_dict_cpu(), seed=3)
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = RP.ReplayBuffer(tcfg, device="cuda")
     lp = LP.C4Loop(sp, tr, rb, tcfg, 16, moves_per_iter=2, train_steps_per_iter=1, model_update_interval=2,
                    concurrent=concurrent, device_ingest=True)
     assert lp.device_ingest and lp.concurrent == concurrent and sp.ingest_buffer is rb

@@ -49,12 +49,12 @@ def _assert_directory_equals_model(rb, model):
 
 def test_directory_equals_a_brute_force_model_of_the_ring():
     """N = 37; 300 random appends of games of 1..40 moves (some longer than the ring): add_arrays with ``game=``,
-    add_arrays without it, and the job tables of whole snapshots (worker.replay_jobs + note_jobs, what
-    GameHistory.ingest does).  After every append each entry's (slot, kept, drop) is what the model's slots say."""
-    from datou_gomoku_muzero_amd import trainer as T
-    from datou_gomoku_muzero_amd.worker import replay_jobs
+    add_arrays without it, and the job tables of whole snapshots (replay.replay_jobs + note_jobs, what
+    ReplayBuffer.ingest_history does).  After every append each entry's (slot, kept, drop) is what the model's slots say."""
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
+    from datou_gomoku_muzero_amd.replay import replay_jobs
     N = 37
-    rb = T.ReplayBuffer(_tcfg(N), device="cpu")
+    rb = RP.ReplayBuffer(_tcfg(N), device="cpu")
     rs = np.random.RandomState(0)
     model, seq, kinds = [None] * N, 0, [0, 0, 0]
     for step in range(300):
@@ -91,8 +91,8 @@ def test_directory_equals_a_brute_force_model_of_the_ring():
 
 
 def test_eligible_orders_by_version_then_append_order_and_cuts_by_age():
-    from datou_gomoku_muzero_amd import trainer as T
-    rb = T.ReplayBuffer(_tcfg(200), device="cpu")
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
+    rb = RP.ReplayBuffer(_tcfg(200), device="cpu")
     for v in (7, 3, 9, 3, 0, 12):
         rb.add_arrays(*_blank_slices(4), game=(1, 0, v))
     key = lambda es: [(e.version, e.seq) for e in es]  # noqa: E731
@@ -114,9 +114,9 @@ def _game_of(rs, n):
 
 def _ring_of(games, pols, vals, N, ptr, extra):
     """A CPU ring at ``ptr`` holding ``extra`` slices of no game and then ``games`` with the given policies/values."""
-    from datou_gomoku_muzero_amd import loop as LP, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, replay as RP, trainer as T
     cfg = _tcfg(N)
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
     rb.ptr, rb.count = ptr, (N if ptr else 0)
     rs = np.random.RandomState(99)
     rb.add_arrays(rs.randint(0, 2, (extra, U + 1, 3, H, H)).astype(np.uint8), rs.randint(0, A, (extra, U)),
@@ -124,7 +124,7 @@ def _ring_of(games, pols, vals, N, ptr, extra):
                   rs.uniform(-1, 1, (extra, U + 1)))
     for (g, p, v) in zip(games, pols, vals):
         _, winner, n, _, _, boards, players, lasts, _, _, acts = g
-        arrs = LP.slices_from_game(boards, players, lasts, p, v, acts, winner, H, cfg.DISCOUNT, cfg.N_STEPS, U)
+        arrs = RP.slices_from_game(boards, players, lasts, p, v, acts, winner, H, cfg.DISCOUNT, cfg.N_STEPS, U)
         rb.add_arrays(*arrs, game=(winner, 0, 0))
     return rb
 
@@ -170,10 +170,10 @@ class _ScriptedReanalyser:
 
 
 def test_c4_loop_runs_the_passes_and_pushes_weights_to_the_reanalyser():
-    from datou_gomoku_muzero_amd import loop as LP, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, replay as RP, trainer as T
     cfg = _tcfg(4096, PHYSICAL_BATCH_SIZE=8, ENABLE_PER=True)
     tr = T.Trainer(cfg, device="cpu")
-    rb = T.ReplayBuffer(cfg, device="cpu")
+    rb = RP.ReplayBuffer(cfg, device="cpu")
     sp, ra = _ScriptedSelfPlay(5), _ScriptedReanalyser()
     lp = LP.C4Loop(sp, tr, rb, cfg, 8, moves_per_iter=2, train_steps_per_iter=1, model_update_interval=2, seed=7,
                    device="cpu", reanalyser=ra, reanalyse_per_iter=3)
@@ -187,7 +187,7 @@ def test_c4_loop_runs_the_passes_and_pushes_weights_to_the_reanalyser():
     assert len(rb.games) == st["games"] > 0 and sum(e.kept for e in rb.games) == len(rb) == st["slices"]
     assert all(e.drop == 0 and e.start == 0 and 0 <= e.version <= st["train_steps"] for e in rb.games)
     # off by default: no re-analyser, no passes, the counters stay in stats()
-    off = LP.C4Loop(_ScriptedSelfPlay(5), tr, T.ReplayBuffer(cfg, device="cpu"), cfg, 8, device="cpu")
+    off = LP.C4Loop(_ScriptedSelfPlay(5), tr, RP.ReplayBuffer(cfg, device="cpu"), cfg, 8, device="cpu")
     off.run(2)
     assert (off.stats()["reanalysed_games"], off.stats()["reanalysed_positions"], off.reanalyse_per_iter) == (0, 0, 0)
 

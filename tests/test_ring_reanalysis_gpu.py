@@ -46,8 +46,8 @@ def _play(rs, H, start, n, winner):
 
 def _random_ring(H, n_steps, N, ptr=0, seed=0):
     """A device ring whose every byte is random (a write outside a game's targets shows), at ``ptr``."""
-    from datou_gomoku_muzero_amd import trainer as T
-    rb = T.ReplayBuffer(_tcfg(H, n_steps, N), device="cuda")
+    from datou_gomoku_muzero_amd import replay as RP, trainer as T
+    rb = RP.ReplayBuffer(_tcfg(H, n_steps, N), device="cuda")
     g = torch.Generator().manual_seed(seed)
     rb.obs.copy_(torch.randint(0, 256, rb.obs.shape, dtype=torch.uint8, generator=g))
     rb.act.copy_(torch.randint(-1, H * H, rb.act.shape, dtype=torch.int32, generator=g))
@@ -59,7 +59,7 @@ def _random_ring(H, n_steps, N, ptr=0, seed=0):
 
 
 def _add(rb, game, pols=None, vals=None):
-    from datou_gomoku_muzero_amd.loop import slices_from_game
+    from datou_gomoku_muzero_amd.replay import slices_from_game
     c, g = rb.cfg, game
     rb.add_arrays(*slices_from_game(g["boards"], g["players"], g["lasts"], g["pols"] if pols is None else pols,
                                     g["vals"] if vals is None else vals, g["acts"], g["winner"], c.BOARD_SIZE, c.DISCOUNT,
@@ -92,7 +92,7 @@ def _assert_ring(rb, want, what):
     (15, 80, 0, 48, [(0, 30), (11, 21)]),
 ])
 def test_positions_kernel_decodes_every_surviving_slice(H, N, ptr, G, shape):
-    from datou_gomoku_muzero_amd import _lib as L, reanalysis as RA
+    from datou_gomoku_muzero_amd import replay as RP
     A = H * H
     rs = np.random.RandomState(H + N)
     rb = _random_ring(H, 10, N, ptr)
@@ -105,7 +105,7 @@ def test_positions_kernel_decodes_every_surviving_slice(H, N, ptr, G, shape):
     if len(games) > 1:  # a surviving first position with no last move
         assert any(games[e.seq]["start"] == 0 and e.drop == 0 for e in rb.games)
     want = [np.concatenate([games[e.seq][k][e.drop:] for e in rb.games]) for k in ("boards", "players", "lasts", "mcs")]
-    rows = RA.ring_rows(rb.games, N)
+    rows = RP.ring_rows(rb.games, N)
     P = len(rows)
     assert P == sum(e.kept for e in rb.games) == len(want[0]) and P % G != 0
     pin = torch.from_numpy(rows).pin_memory()
@@ -115,7 +115,7 @@ def test_positions_kernel_decodes_every_surviving_slice(H, N, ptr, G, shape):
         n = min(G, P - lo)
         out = (torch.full((G, A), 7, dtype=torch.int8, device="cuda"), torch.full((G,), 7, dtype=torch.int8, device="cuda"),
                torch.full((G,), 7, dtype=torch.int32, device="cuda"), torch.full((G,), 7, dtype=torch.int32, device="cuda"))
-        L.replay_positions(rb, pin[lo:lo + n], dev[lo:lo + n], n, *out)
+        rb.decode_positions(pin[lo:lo + n], dev[lo:lo + n], n, *out)
         torch.cuda.synchronize()
         for k, t in enumerate(out):
             got[k].append(t[:n].cpu())
@@ -126,7 +126,7 @@ def test_positions_kernel_decodes_every_surviving_slice(H, N, ptr, G, shape):
                 assert torch.equal(t[n:].cpu(), w)
     for k, name in enumerate(("board", "player", "last move", "move count")):
         assert torch.equal(torch.cat(got[k]), torch.from_numpy(want[k])), name
-    host = RA.ring_positions_host(rb, rows)  # the host path's decode is the same function of the ring
+    host = RP.ring_positions_host(rb, rows)  # the host path's decode is the same function of the ring
     for k in range(4):
         assert np.array_equal(host[k].reshape(want[k].shape), want[k])
 
@@ -168,7 +168,6 @@ def test_rewrite_kernel_equals_host_rewrite(n_steps, layout):
     """lengths: 5x5, games of 1, 2, U, U+1, n_steps, n_steps+1 and A moves, winners -1, 0 and 1, and a resident game
     of 8 moves that is not in the job table.  wrap: N = 37 at ptr 30, the first game trimmed to its last 3 slices,
     the last one wrapping the ring's end, three games in one launch and a resident one left out.  15x15: A = 225."""
-    from datou_gomoku_muzero_amd import _lib as L
     H, N, ptr, shape, skip = {
         "lengths": (5, 256, 0, [(0, 1), (1, 2), (0, U), (2, 8), (3, U + 1), (0, n_steps), (1, n_steps + 1), (0, 25)], 3),
         "wrap": (5, 37, 30, [(0, 12), (3, 20), (1, 5), (0, 9)], 1),
@@ -182,7 +181,7 @@ def test_rewrite_kernel_equals_host_rewrite(n_steps, layout):
     P = len(val)
     pin, tab = _tables(entries)
     before = _snap(dev)
-    L.replay_rewrite(dev, torch.from_numpy(pol).cuda(), torch.from_numpy(val).cuda(), P, pin, tab, len(entries))
+    dev.rewrite_games(torch.from_numpy(pol).cuda(), torch.from_numpy(val).cuda(), P, pin, tab, len(entries))
     host.rewrite_games_host([e for e in host.games if e.seq != skip], pol, val)
     _assert_ring(dev, host, layout)
     for k in ("obs", "act", "rew", "prio"):
@@ -205,18 +204,18 @@ def test_rewrite_kernel_refusals_leave_the_ring_unchanged():
     before = _snap(dev)
     pin, tab = _tables(entries)
     cases = {
-        "overlap": lambda: L.replay_rewrite(dev, pol_d, val_d, P, *_tables(entries, {(1, 0): 3}), 2),  # 30..4 and 3..22
-        "staged row": lambda: L.replay_rewrite(dev, pol_d, val_d, P - 1, pin, tab, 2),
-        "pol_new": lambda: L.replay_rewrite(dev, pol_d[:P - 1], val_d, P, pin, tab, 2),
-        "val_new": lambda: L.replay_rewrite(dev, pol_d, val_d[:P - 1], P, pin, tab, 2),
-        "job table": lambda: L.replay_rewrite(dev, pol_d, val_d, P, pin, tab[:1], 2),
-        "kept": lambda: L.replay_rewrite(dev, pol_d, val_d, P, *_tables(entries, {(1, 1): 38, (1, 2): 38}), 2),  # > N
+        "overlap": lambda: dev.rewrite_games(pol_d, val_d, P, *_tables(entries, {(1, 0): 3}), 2),  # 30..4 and 3..22
+        "staged row": lambda: dev.rewrite_games(pol_d, val_d, P - 1, pin, tab, 2),
+        "pol_new": lambda: dev.rewrite_games(pol_d[:P - 1], val_d, P, pin, tab, 2),
+        "val_new": lambda: dev.rewrite_games(pol_d, val_d[:P - 1], P, pin, tab, 2),
+        "job table": lambda: dev.rewrite_games(pol_d, val_d, P, pin, tab[:1], 2),
+        "kept": lambda: dev.rewrite_games(pol_d, val_d, P, *_tables(entries, {(1, 1): 38, (1, 2): 38}), 2),  # > N
     }
     for word, call in cases.items():
         with pytest.raises(L.GmzError, match=word):
             call()
         _assert_ring(dev, before, "after the refusal of a bad %s" % word)
-    L.replay_rewrite(dev, pol_d, val_d, P, pin, tab, 2)  # and the good call goes through
+    dev.rewrite_games(pol_d, val_d, P, pin, tab, 2)  # and the good call goes through
     torch.cuda.synchronize()
     assert not torch.equal(dev.pol, before["pol"])
 
@@ -306,14 +305,14 @@ def test_c4_loop_reanalyses_its_shard(concurrent):
     the trainer on its own stream.  The staging holds the whole ring of 256 slices, so every pass re-searches every
     game in it: afterwards every entry carries the last pass's step, and every game's ring targets are the n-step
     returns of the values (and the policies) that pass staged."""
-    from datou_gomoku_muzero_amd import loop as LP, records as R, reanalysis as RA, trainer as T
+    from datou_gomoku_muzero_amd import loop as LP, records as R, reanalysis as RA, replay as RP, trainer as T
     from datou_gomoku_muzero_amd.config import GmzConfig
     N = 256
     cfg = GmzConfig(BOARD_SIZE=6, NUM_SIMULATIONS=16, NUM_RES_BLOCKS=1, REANALYSIS_AGE_THRESHOLD=0)
     tcfg = T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, PHYSICAL_BATCH_SIZE=16, TRAIN_BUFFER_SIZE=N, ENABLE_PER=True)
     tr = T.Trainer(tcfg, device="cuda") if concurrent else T.Trainer(tcfg, device="cuda", graph=False)
     sp = LP.SelfPlay(cfg, 32, tr.state_dict_cpu(), seed=3)
-    rb = T.ReplayBuffer(tcfg, device="cuda")
+    rb = RP.ReplayBuffer(tcfg, device="cuda")
     ra = RA.RingReanalyser(cfg, rb, tr.state_dict_cpu(), num_games=64, max_positions=N, seed=5)
     lp = LP.C4Loop(sp, tr, rb, tcfg, 16, moves_per_iter=2, train_steps_per_iter=1, model_update_interval=2,
                    concurrent=concurrent, device_ingest=True, reanalyser=ra, reanalyse_per_iter=1)

@@ -23,12 +23,12 @@ sys.path.insert(0, REPO)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from datou_gomoku_muzero_amd import trainer as T, weights as W  # noqa: E402
+from datou_gomoku_muzero_amd import replay as RP, trainer as T, weights as W  # noqa: E402
 
 
 def full_ring(cfg, capacity, seed):
     """A full device ring: 4,096 synthetic slices repeated on the device, priorities |x| + 1e-6."""
-    rb = T.ReplayBuffer(cfg, capacity=capacity, device="cuda")
+    rb = RP.ReplayBuffer(cfg, capacity=capacity, device="cuda")
     n = min(4096, capacity)
     rb.add_arrays(*W.synthetic_slices(n, cfg.BOARD_SIZE, cfg.NUM_UNROLL_STEPS, np.random.RandomState(seed)))
     for t in (rb.obs, rb.act, rb.rew, rb.pol, rb.val):

@@ -74,7 +74,7 @@ dist = None
 if world > 1:
     import torch.distributed as dist
     dist.init_process_group(os.environ.get("GMZ_DIST_BACKEND", "nccl"), init_method="env://")
-from datou_gomoku_muzero_amd import trainer as T  # noqa: E402
+from datou_gomoku_muzero_amd import replay as RP, trainer as T  # noqa: E402
 
 T.HIP_WGRAD = T.HIP_WGRAD and not a.miopen_wgrad
 T.CONCURRENT_FORWARD = T.CONCURRENT_FORWARD and not a.sequential_forward
@@ -100,7 +100,7 @@ cfg = T.TrainConfig(BOARD_SIZE=a.size, NUM_RES_BLOCKS=a.blocks, PHYSICAL_BATCH_S
                     TRAIN_BUFFER_SIZE=a.buffer, ENABLE_PER=a.per)
 tr = T.Trainer(cfg, device="cuda", amp=not a.no_amp, amp_dtype=torch.bfloat16 if a.bf16 else None,
                channels_last=a.channels_last, graph=not a.eager)
-rb = T.ReplayBuffer(cfg, device="cuda")
+rb = RP.ReplayBuffer(cfg, device="cuda")
 S = namedtuple("S", "observation action_history reward_history policy_history value_history")
 rs = np.random.RandomState(rank)
 U, A = cfg.NUM_UNROLL_STEPS, a.size * a.size

@@ -22,7 +22,7 @@ sys.path.insert(0, REPO)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from datou_gomoku_muzero_amd import loop as LP, worker as WK  # noqa: E402
+from datou_gomoku_muzero_amd import loop as LP, replay as RP  # noqa: E402
 
 
 def namespace(a, train_per_iter, device_ingest, iters=None):
@@ -48,23 +48,23 @@ def run(a, train_per_iter, device_ingest, emit, label=None, iters=None):
 
 
 def timed_ingest(a, emit):
-    """One device-ingest run with every GameHistory.ingest call between two device events."""
+    """One device-ingest run with every ReplayBuffer.ingest_history call between two device events."""
     marks = []
-    ingest = WK.GameHistory.ingest
+    ingest = RP.ReplayBuffer.ingest_history
 
-    def bracketed(self, sn, rb, games=None):
-        st = torch.cuda.current_stream(self.dev)
+    def bracketed(self, hist, sn, games=None):
+        st = torch.cuda.current_stream(hist.dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(st)
-        got = ingest(self, sn, rb, games=games)
+        got = ingest(self, hist, sn, games=games)
         e1.record(st)
         marks.append((e0, e1, len(got), sum(x[2] for x in got)))
         return got
-    WK.GameHistory.ingest = bracketed
+    RP.ReplayBuffer.ingest_history = bracketed
     try:
         run(a, 1, True, emit, label="ingest bracketed by device events")
     finally:
-        WK.GameHistory.ingest = ingest
+        RP.ReplayBuffer.ingest_history = ingest
     torch.cuda.synchronize()
     rows = [(e0.elapsed_time(e1) * 1e3, g, s) for (e0, e1, g, s) in marks if g > 0]
     if rows:

@@ -2,10 +2,10 @@
 priority update) on C4: shows whether the host or the GPU bounds the step (the logs read waits for the GPU)."""
 import sys, time, numpy as np, torch
 sys.path.insert(0, '.')
-from datou_gomoku_muzero_amd import trainer as T
+from datou_gomoku_muzero_amd import replay as RP, trainer as T
 cfg = T.TrainConfig(BOARD_SIZE=15, NUM_RES_BLOCKS=8, PHYSICAL_BATCH_SIZE=360, TRAIN_BUFFER_SIZE=4096, ENABLE_PER=True)
 from datou_gomoku_muzero_amd import weights as W
-rb = T.ReplayBuffer(cfg, device="cuda"); rs = np.random.RandomState(0)
+rb = RP.ReplayBuffer(cfg, device="cuda"); rs = np.random.RandomState(0)
 rb.add_arrays(*W.synthetic_slices(4096, 15, cfg.NUM_UNROLL_STEPS, rs))
 tr = T.Trainer(cfg, device="cuda")
 pend = None

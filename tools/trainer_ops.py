@@ -16,11 +16,11 @@ ap.add_argument("--batch", type=int, default=360)
 ap.add_argument("--top", type=int, default=60)
 a = ap.parse_args()
 torch.backends.cudnn.benchmark = True
-from datou_gomoku_muzero_amd import trainer as T  # noqa: E402
+from datou_gomoku_muzero_amd import replay as RP, trainer as T  # noqa: E402
 
 cfg = T.TrainConfig(BOARD_SIZE=15, NUM_RES_BLOCKS=8, PHYSICAL_BATCH_SIZE=a.batch, TRAIN_BUFFER_SIZE=2000)
 tr = T.Trainer(cfg, device="cuda", graph=False)
-rb = T.ReplayBuffer(cfg, device="cuda")
+rb = RP.ReplayBuffer(cfg, device="cuda")
 S = namedtuple("S", "observation action_history reward_history policy_history value_history")
 rs = np.random.RandomState(0)
 U, A = cfg.NUM_UNROLL_STEPS, 225
