@@ -1214,6 +1214,8 @@ GMZ_EXPORT int gmz_conv3x3_pack(int dtype, const float *w, int64_t s0, int64_t s
                                 int transpose, void *packed, void *stream) {
   if (!w || !packed) return fail("gmz_conv3x3_pack: null operand");
   if (dtype != 1 && dtype != 2) return fail("gmz_conv3x3_pack: dtype must be 1 (f16) or 2 (bf16)");
+  // the kernel writes 16-byte fragments, as gmz_conv3x3_pack_split checks
+  if ((uintptr_t)packed & 15) return fail("gmz_conv3x3_pack: packed must be 16-B aligned");
   hipStream_t st = (hipStream_t)stream;
   const int n = CKSTEPS * 8 * 64;
   if (dtype == 1)

@@ -424,7 +424,15 @@ int gmz_bn_eval(int dtype, int layout, const void *x_dev, const void *res_dev, i
  * gradient dx = conv(dy, W') with W'[c][o][t] = W[o][c][8 - t].
  * gmz_conv3x3_pack: f32 weight W[o][c][ky][kx] at element strides (s0, s1, s2, s3) -> packed_dev
  *   (294,912 bytes, 16-B aligned) in MFMA fragment order; transpose = 1 packs W'.
- * gmz_conv3x3_forward: x_dev, packed_dev and y_dev 16-B aligned, N >= 1. */
+ *   A packed_dev off the 16-byte grid is refused before the launch.
+ * gmz_conv3x3_forward: x_dev, packed_dev and y_dev 16-B aligned, N >= 1.
+ * Arithmetic, every entry point of the family (tests/conv_ref.py is its float64 restatement): the packed weights
+ * are W (or W') rounded to nearest even into dtype; every product is exact in f32; the output element is ONE
+ * rounding to nearest even of the f32 sum (plus the stamp's table entry and the addend, where given, added in f32
+ * before it).  A sum that is exactly zero is stored as +0.0 (the accumulators start at +0.0), also where a weight
+ * rounded to -0.0.
+ * mask_dev selects what the STATISTICS count and nothing else: y of a board whose mask byte is zero is still
+ * written, the same convolution as with mask_dev NULL (and gmz_conv3x3_forward_bnapply still writes its bn_y). */
 int gmz_conv3x3_pack(int dtype, const float *w_dev, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int transpose,
                      void *packed_dev, void *stream);
 /* gmz_conv3x3_pack of n_jobs weights in one launch: jobs_dev (device memory, gmz_conv3x3_pack_job_bytes each) =
