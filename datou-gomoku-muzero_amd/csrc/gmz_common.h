@@ -1,5 +1,7 @@
 // gmz_common.h — shared helpers for the gfx950 kernels of libgmz.so (internal, not part of the ABI).
 #pragma once
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
@@ -22,6 +24,26 @@ int fail(const std::string &msg);  // set_error + return -1
   } while (0)
 
 #define GMZ_LAUNCH_CHECK() GMZ_HIP(hipGetLastError())
+
+// The one dtype dispatch of the C boundary: f(DType<T>{}) with T the element type of an entry point's dtype argument
+// (0 = float where AllowF32, 1 = __half, 2 = __hip_bfloat16), else "<prefix>: dtype must be ...".  The prefix is the
+// caller's, because the reported name is not always the entry point's own.  f returns what its launcher
+// returns (GMZ_LAUNCH_CHECK inside f leaves f only), and by_dtype hands that value on.
+template <typename T>
+struct DType {
+  using type = T;
+};
+template <typename Tag>
+using dtype_of = typename Tag::type;  // inside f: using T = dtype_of<decltype(t)>
+template <bool AllowF32, typename F>
+int by_dtype(const char *prefix, int dtype, F &&f) {
+  if constexpr (AllowF32) {
+    if (dtype == 0) return f(DType<float>{});
+  }
+  if (dtype == 1) return f(DType<__half>{});
+  if (dtype == 2) return f(DType<__hip_bfloat16>{});
+  return fail(std::string(prefix) + ": dtype must be " + (AllowF32 ? "0 (f32), " : "") + "1 (f16) or 2 (bf16)");
+}
 
 constexpr int WAVE = 64;
 

@@ -21,6 +21,7 @@
 // image is 117 KB, so one workgroup per CU; the weight gradient there stages each board in two row bands (WgLds).
 // k_conv3_split (below k_conv3) is the same convolution on float32 activations with split-f16 operands, float32-grade:
 // the target network's value trunk (gmz_conv3x3_forward_split).
+#include <initializer_list>
 #include <type_traits>
 
 #include "gmz_common.h"
@@ -1171,14 +1172,31 @@ int launch_conv3(const void *x, const void *wpk, void *y, int N, const uint8_t *
   return 0;
 }
 
-template <typename T>
-int conv3_dispatch(int H, const void *x, const void *wpk, void *y, int N, const uint8_t *mask, double *stats, const void *addend,
-                   hipStream_t st, const BnBwd &bn = BnBwd{}, bool per_board = false, const ActStamp &as = ActStamp{},
-                   const BnApply &ba = BnApply{}) {
-  const int rc = for_size(H, ConvSizes{}, [&](auto h) {
-    return launch_conv3<decltype(h)::value, T>(x, wpk, y, N, mask, stats, addend, bn, st, per_board, as, ba);
+// The one host path of the gmz_conv3x3_forward* entry points.  In this order: the operands of `need` non-null, N,
+// `early`, the statistics slots (one per board pair of workgroups, or per board), the operands of `aligned` 16-B
+// aligned, `late`, then dtype and board size into launch_conv3.  fn is the entry point's name (the slot check reports
+// it), pfx what the other messages carry; early / late are an entry point's own refusal, worked out by it and reported
+// here at its place in the order (empty: none).
+int conv3_forward(const char *fn, const char *pfx, int dtype, int H, std::initializer_list<const void *> need,
+                  std::initializer_list<const void *> aligned, const std::string &early, const std::string &late,
+                  const void *x, const void *wpk, void *y, int N, const uint8_t *mask, double *stats, int stats_slots,
+                  bool per_board, const void *addend, void *stream, const BnBwd &bn = BnBwd{},
+                  const ActStamp &as = ActStamp{}, const BnApply &ba = BnApply{}) {
+  for (const void *p : need)
+    if (!p) return fail(std::string(pfx) + ": null operand");
+  if (N <= 0) return fail(std::string(pfx) + ": N must be positive");
+  if (!early.empty()) return fail(early);
+  if (check_slots(fn, stats, stats_slots, N, per_board)) return -1;
+  for (const void *p : aligned)
+    if ((uintptr_t)p & 15) return fail(std::string(pfx) + ": operands must be 16-B aligned");
+  if (!late.empty()) return fail(late);
+  return by_dtype<false>(pfx, dtype, [&](auto t) {
+    const int rc = for_size(H, ConvSizes{}, [&](auto h) {
+      return launch_conv3<decltype(h)::value, dtype_of<decltype(t)>>(x, wpk, y, N, mask, stats, addend, bn,
+                                                                     (hipStream_t)stream, per_board, as, ba);
+    });
+    return rc == -2 ? bad_size("gmz_conv3x3") : rc;
   });
-  return rc == -2 ? bad_size("gmz_conv3x3") : rc;
 }
 
 template <int H>
@@ -1213,19 +1231,15 @@ using namespace gmz;
 GMZ_EXPORT int gmz_conv3x3_pack(int dtype, const float *w, int64_t s0, int64_t s1, int64_t s2, int64_t s3,
                                 int transpose, void *packed, void *stream) {
   if (!w || !packed) return fail("gmz_conv3x3_pack: null operand");
-  if (dtype != 1 && dtype != 2) return fail("gmz_conv3x3_pack: dtype must be 1 (f16) or 2 (bf16)");
-  // the kernel writes 16-byte fragments, as gmz_conv3x3_pack_split checks
-  if ((uintptr_t)packed & 15) return fail("gmz_conv3x3_pack: packed must be 16-B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int n = CKSTEPS * 8 * 64;
-  if (dtype == 1)
-    hipLaunchKernelGGL(k_pack_conv<__half>, dim3((n + 255) / 256), dim3(256), 0, st, w, (long)s0, (long)s1, (long)s2,
-                       (long)s3, transpose, (uint16_t *)packed);
-  else
-    hipLaunchKernelGGL(k_pack_conv<__hip_bfloat16>, dim3((n + 255) / 256), dim3(256), 0, st, w, (long)s0, (long)s1,
-                       (long)s2, (long)s3, transpose, (uint16_t *)packed);
-  GMZ_LAUNCH_CHECK();
-  return 0;
+  return by_dtype<false>("gmz_conv3x3_pack", dtype, [&](auto t) {  // the dtype is checked before the alignment
+    // the kernel writes 16-byte fragments, as gmz_conv3x3_pack_split checks
+    if ((uintptr_t)packed & 15) return fail("gmz_conv3x3_pack: packed must be 16-B aligned");
+    const int n = CKSTEPS * 8 * 64;
+    hipLaunchKernelGGL(k_pack_conv<dtype_of<decltype(t)>>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
+                       (long)s0, (long)s1, (long)s2, (long)s3, transpose, (uint16_t *)packed);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_conv3x3_pack_job_bytes(size_t *out) {
@@ -1236,13 +1250,12 @@ GMZ_EXPORT int gmz_conv3x3_pack_job_bytes(size_t *out) {
 
 GMZ_EXPORT int gmz_conv3x3_pack_many(int dtype, const void *jobs, int n_jobs, void *stream) {
   if (!jobs || n_jobs <= 0 || n_jobs > 65535) return fail("gmz_conv3x3_pack_many: 1 <= n_jobs <= 65535 jobs");
-  hipStream_t st = (hipStream_t)stream;
   const dim3 grid((CKSTEPS * 8 * 64 + 255) / 256, n_jobs);
-  if (dtype == 1) hipLaunchKernelGGL(k_pack_many<__half>, grid, dim3(256), 0, st, (const PackJob *)jobs);
-  else if (dtype == 2) hipLaunchKernelGGL(k_pack_many<__hip_bfloat16>, grid, dim3(256), 0, st, (const PackJob *)jobs);
-  else return fail("gmz_conv3x3_pack_many: dtype must be 1 (f16) or 2 (bf16)");
-  GMZ_LAUNCH_CHECK();
-  return 0;
+  return by_dtype<false>("gmz_conv3x3_pack_many", dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_pack_many<dtype_of<decltype(t)>>, grid, dim3(256), 0, (hipStream_t)stream, (const PackJob *)jobs);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_conv3x3_pack_split(const float *w, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int transpose,
@@ -1294,67 +1307,42 @@ GMZ_EXPORT int gmz_conv3x3_stats_slots(int N, int *slots) {
 
 GMZ_EXPORT int gmz_conv3x3_forward_stats(int dtype, int H, const void *x, const void *packed, void *y, int N,
                                          const uint8_t *mask, double *stats, int stats_slots, void *stream) {
-  if (!x || !packed || !y) return fail("gmz_conv3x3_forward: null operand");
-  if (N <= 0) return fail("gmz_conv3x3_forward: N must be positive");
-  if (check_slots("gmz_conv3x3_forward_stats", stats, stats_slots, N, false)) return -1;
-  if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)y) & 15) return fail("gmz_conv3x3_forward: operands must be 16-B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == 1) return conv3_dispatch<__half>(H, x, packed, y, N, mask, stats, nullptr, st);
-  if (dtype == 2) return conv3_dispatch<__hip_bfloat16>(H, x, packed, y, N, mask, stats, nullptr, st);
-  return fail("gmz_conv3x3_forward: dtype must be 1 (f16) or 2 (bf16)");
+  return conv3_forward("gmz_conv3x3_forward_stats", "gmz_conv3x3_forward", dtype, H, {x, packed, y}, {x, packed, y}, "", "",
+                       x, packed, y, N, mask, stats, stats_slots, false, nullptr, stream);
 }
 
 GMZ_EXPORT int gmz_conv3x3_forward_board_stats(int dtype, int H, const void *x, const void *packed, void *y, int N,
                                                const uint8_t *mask, double *stats, int stats_slots, void *stream) {
-  if (!x || !packed || !y || !stats) return fail("gmz_conv3x3_forward_board_stats: null operand");
-  if (N <= 0) return fail("gmz_conv3x3_forward_board_stats: N must be positive");
-  if (check_slots("gmz_conv3x3_forward_board_stats", stats, stats_slots, N, true)) return -1;
-  if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)y) & 15)
-    return fail("gmz_conv3x3_forward_board_stats: operands must be 16-B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == 1) return conv3_dispatch<__half>(H, x, packed, y, N, mask, stats, nullptr, st, BnBwd{}, true);
-  if (dtype == 2) return conv3_dispatch<__hip_bfloat16>(H, x, packed, y, N, mask, stats, nullptr, st, BnBwd{}, true);
-  return fail("gmz_conv3x3_forward_board_stats: dtype must be 1 (f16) or 2 (bf16)");
+  const char *fn = "gmz_conv3x3_forward_board_stats";
+  return conv3_forward(fn, fn, dtype, H, {x, packed, y, stats}, {x, packed, y}, "", "", x, packed, y, N, mask, stats,
+                       stats_slots, true, nullptr, stream);
 }
 
 GMZ_EXPORT int gmz_conv3x3_forward_stamp(int dtype, int H, const void *x, const void *packed, void *y, int N,
                                          const uint8_t *mask, double *stats, int stats_slots, const int32_t *action,
                                          const void *table, int table_dtype, size_t table_bytes, void *stream) {
-  if (!x || !packed || !y || !action || !table) return fail("gmz_conv3x3_forward_stamp: null operand");
-  if (N <= 0) return fail("gmz_conv3x3_forward_stamp: N must be positive");
-  // the kernel reads the table as f32 [9][128]: any other dtype or size fails here, before the launch (ABI 10; the
+  const char *fn = "gmz_conv3x3_forward_stamp";
+  // the kernel reads the table as f32 [9][128]: any other dtype or size fails before the launch (ABI 10; the
   // round-5 faults were an f16 table built inside autocast, read past its 2,304 bytes)
-  if (table_dtype != 0) return fail("gmz_conv3x3_forward_stamp: table_dtype must be 0 (f32)");
-  if (table_bytes != (size_t)9 * CC * sizeof(float))
-    return fail("gmz_conv3x3_forward_stamp: table of " + std::to_string(table_bytes) + " bytes, must be f32 [9][128] = 4608");
-  if (check_slots("gmz_conv3x3_forward_stamp", stats, stats_slots, N, false)) return -1;
-  if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)y) & 15)
-    return fail("gmz_conv3x3_forward_stamp: operands must be 16-B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const ActStamp as = {action, (const float *)table};
-  if (dtype == 1) return conv3_dispatch<__half>(H, x, packed, y, N, mask, stats, nullptr, st, BnBwd{}, false, as);
-  if (dtype == 2) return conv3_dispatch<__hip_bfloat16>(H, x, packed, y, N, mask, stats, nullptr, st, BnBwd{}, false, as);
-  return fail("gmz_conv3x3_forward_stamp: dtype must be 1 (f16) or 2 (bf16)");
+  std::string table_err;
+  if (table_dtype != 0) table_err = "gmz_conv3x3_forward_stamp: table_dtype must be 0 (f32)";
+  else if (table_bytes != (size_t)9 * CC * sizeof(float))
+    table_err = "gmz_conv3x3_forward_stamp: table of " + std::to_string(table_bytes) + " bytes, must be f32 [9][128] = 4608";
+  return conv3_forward(fn, fn, dtype, H, {x, packed, y, action, table}, {x, packed, y}, table_err, "", x, packed, y, N, mask,
+                       stats, stats_slots, false, nullptr, stream, BnBwd{}, ActStamp{action, (const float *)table});
 }
 
 GMZ_EXPORT int gmz_conv3x3_forward_bnapply(int dtype, int H, const void *bn_x, const void *bn_res, const float *gamma,
                                            const float *beta, const float *bn_save, int relu, void *bn_y,
                                            const void *packed, void *y, int N, const uint8_t *mask, double *stats,
                                            int stats_slots, void *stream) {
-  if (!bn_x || !gamma || !beta || !bn_save || !bn_y || !packed || !y)
-    return fail("gmz_conv3x3_forward_bnapply: null operand");
-  if (N <= 0) return fail("gmz_conv3x3_forward_bnapply: N must be positive");
-  if (check_slots("gmz_conv3x3_forward_bnapply", stats, stats_slots, N, false)) return -1;
-  if (((uintptr_t)bn_x | (uintptr_t)bn_res | (uintptr_t)bn_y | (uintptr_t)packed | (uintptr_t)y) & 15)
-    return fail("gmz_conv3x3_forward_bnapply: operands must be 16-B aligned");
-  if (bn_y == bn_x || bn_y == bn_res || bn_y == y || y == bn_x)
-    return fail("gmz_conv3x3_forward_bnapply: the BatchNorm output, its input and the conv output must not alias");
-  hipStream_t st = (hipStream_t)stream;
+  const char *fn = "gmz_conv3x3_forward_bnapply";
+  const bool alias = bn_y == bn_x || bn_y == bn_res || bn_y == y || y == bn_x;
   const BnApply ba = {(const uint16_t *)bn_x, (const uint16_t *)bn_res, gamma, beta, bn_save, (uint16_t *)bn_y, relu};
-  if (dtype == 1) return conv3_dispatch<__half>(H, bn_y, packed, y, N, mask, stats, nullptr, st, BnBwd{}, false, ActStamp{}, ba);
-  if (dtype == 2)
-    return conv3_dispatch<__hip_bfloat16>(H, bn_y, packed, y, N, mask, stats, nullptr, st, BnBwd{}, false, ActStamp{}, ba);
-  return fail("gmz_conv3x3_forward_bnapply: dtype must be 1 (f16) or 2 (bf16)");
+  return conv3_forward(fn, fn, dtype, H, {bn_x, gamma, beta, bn_save, bn_y, packed, y}, {bn_x, bn_res, bn_y, packed, y}, "",
+                       alias ? "gmz_conv3x3_forward_bnapply: the BatchNorm output, its input and the conv output must not alias"
+                             : "",
+                       bn_y, packed, y, N, mask, stats, stats_slots, false, nullptr, stream, BnBwd{}, ActStamp{}, ba);
 }
 
 GMZ_EXPORT int gmz_conv3x3_forward(int dtype, int H, const void *x, const void *packed, void *y, int N, void *stream) {
@@ -1363,31 +1351,21 @@ GMZ_EXPORT int gmz_conv3x3_forward(int dtype, int H, const void *x, const void *
 
 GMZ_EXPORT int gmz_conv3x3_forward_add(int dtype, int H, const void *x, const void *packed, const void *addend, void *y,
                                        int N, void *stream) {
-  if (!x || !packed || !y || !addend) return fail("gmz_conv3x3_forward_add: null operand");
-  if (N <= 0) return fail("gmz_conv3x3_forward_add: N must be positive");
-  if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)y | (uintptr_t)addend) & 15)
-    return fail("gmz_conv3x3_forward_add: operands must be 16-B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == 1) return conv3_dispatch<__half>(H, x, packed, y, N, nullptr, nullptr, addend, st);
-  if (dtype == 2) return conv3_dispatch<__hip_bfloat16>(H, x, packed, y, N, nullptr, nullptr, addend, st);
-  return fail("gmz_conv3x3_forward_add: dtype must be 1 (f16) or 2 (bf16)");
+  const char *fn = "gmz_conv3x3_forward_add";
+  return conv3_forward(fn, fn, dtype, H, {x, packed, y, addend}, {x, packed, y, addend}, "", "", x, packed, y, N, nullptr,
+                       nullptr, 0, false, addend, stream);
 }
 
 GMZ_EXPORT int gmz_conv3x3_forward_bwdstats(int dtype, int H, const void *x, const void *packed, const void *addend,
                                             void *y, int N, const uint8_t *mask, const void *bn_x, const void *bn_y,
                                             const float *bn_save, int relu, double *stats, int stats_slots,
                                             void *stream) {
-  if (!x || !packed || !y || !bn_x || !bn_y || !bn_save || !stats) return fail("gmz_conv3x3_forward_bwdstats: null operand");
-  if (N <= 0) return fail("gmz_conv3x3_forward_bwdstats: N must be positive");
-  if (check_slots("gmz_conv3x3_forward_bwdstats", stats, stats_slots, N, false)) return -1;
-  if (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)y | (uintptr_t)addend) & 15)
-    return fail("gmz_conv3x3_forward_bwdstats: operands must be 16-B aligned");
-  if (((uintptr_t)bn_x | (uintptr_t)bn_y) & 7) return fail("gmz_conv3x3_forward_bwdstats: BN operands must be 8-B aligned");
-  hipStream_t st = (hipStream_t)stream;
+  const char *fn = "gmz_conv3x3_forward_bwdstats";
+  const bool bn_odd = (((uintptr_t)bn_x | (uintptr_t)bn_y) & 7) != 0;
   const BnBwd bn = {(const uint16_t *)bn_x, (const uint16_t *)bn_y, bn_save, relu};
-  if (dtype == 1) return conv3_dispatch<__half>(H, x, packed, y, N, mask, stats, addend, st, bn);
-  if (dtype == 2) return conv3_dispatch<__hip_bfloat16>(H, x, packed, y, N, mask, stats, addend, st, bn);
-  return fail("gmz_conv3x3_forward_bwdstats: dtype must be 1 (f16) or 2 (bf16)");
+  return conv3_forward(fn, fn, dtype, H, {x, packed, y, bn_x, bn_y, bn_save, stats}, {x, packed, y, addend}, "",
+                       bn_odd ? "gmz_conv3x3_forward_bwdstats: BN operands must be 8-B aligned" : "", x, packed, y, N, mask,
+                       stats, stats_slots, false, addend, stream, bn);
 }
 
 GMZ_EXPORT int gmz_conv3x3_wgrad_workspace_bytes(int N, size_t *out) {
@@ -1404,12 +1382,11 @@ static int wgrad_launch(int dtype, int H, const WgSrc &src, int N, float *dw, in
     return fail("gmz_conv3x3_wgrad: workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(N) +
                 " boards need " + std::to_string(need) + " (gmz_conv3x3_wgrad_workspace_bytes)");
   float *part = (float *)workspace;
-  int rc;
-  if (dtype == 1)
-    rc = for_size(H, ConvSizes{}, [&](auto h) { return launch_wgrad<decltype(h)::value, __half>(src, N, part, st); });
-  else if (dtype == 2)
-    rc = for_size(H, ConvSizes{}, [&](auto h) { return launch_wgrad<decltype(h)::value, __hip_bfloat16>(src, N, part, st); });
-  else return fail("gmz_conv3x3_wgrad: dtype must be 1 (f16) or 2 (bf16)");
+  const int rc = by_dtype<false>("gmz_conv3x3_wgrad", dtype, [&](auto t) {
+    return for_size(H, ConvSizes{}, [&](auto h) {
+      return launch_wgrad<decltype(h)::value, dtype_of<decltype(t)>>(src, N, part, st);
+    });
+  });
   if (rc) return rc;
   hipLaunchKernelGGL(k_conv3_wgrad_reduce, dim3((9 * CC * CC + 255) / 256), dim3(256), 0, st, (const float *)part,
                      wgrad_chunks(N), dw, (long)s0, (long)s1, (long)s2, (long)s3, accumulate);

@@ -16,6 +16,7 @@
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
+#include <limits.h>
 
 namespace gmz {
 namespace {
@@ -250,13 +251,9 @@ GMZ_EXPORT int gmz_head_conv1x1_forward(int dtype, const void *x, long P, int C,
   if (head_check("gmz_head_conv1x1_forward", C, P, O0, O1, x, w0, w1)) return -1;
   const HeadW hw{w0, b0, w1, b1};
   if (!y0 || (O1 > 0 && !y1)) return fail("gmz_head_conv1x1_forward: null output");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return head_fwd<float>(x, P, hw, O0, O1, y0, y1, st);
-    case 1: return head_fwd<__half>(x, P, hw, O0, O1, y0, y1, st);
-    case 2: return head_fwd<__hip_bfloat16>(x, P, hw, O0, O1, y0, y1, st);
-  }
-  return fail("gmz_head_conv1x1_forward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return by_dtype<true>("gmz_head_conv1x1_forward", dtype, [&](auto t) {
+    return head_fwd<dtype_of<decltype(t)>>(x, P, hw, O0, O1, y0, y1, (hipStream_t)stream);
+  });
 }
 
 GMZ_EXPORT int gmz_head_conv1x1_workspace_bytes(long P, int O, size_t *out) {
@@ -278,14 +275,10 @@ GMZ_EXPORT int gmz_head_conv1x1_backward(int dtype, const void *x, long P, int C
                   std::to_string(need) + " (gmz_head_conv1x1_workspace_bytes)");
   }
   if (((uintptr_t)dx) % 16) return fail("gmz_head_conv1x1_backward: dx must be 16-B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return head_bwd<float>(x, P, hw, O0, O1, dy0, dy1, dx, dw0, db0, dw1, db1, accumulate, (float *)ws, st);
-    case 1: return head_bwd<__half>(x, P, hw, O0, O1, dy0, dy1, dx, dw0, db0, dw1, db1, accumulate, (float *)ws, st);
-    case 2:
-      return head_bwd<__hip_bfloat16>(x, P, hw, O0, O1, dy0, dy1, dx, dw0, db0, dw1, db1, accumulate, (float *)ws, st);
-  }
-  return fail("gmz_head_conv1x1_backward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return by_dtype<true>("gmz_head_conv1x1_backward", dtype, [&](auto t) {
+    return head_bwd<dtype_of<decltype(t)>>(x, P, hw, O0, O1, dy0, dy1, dx, dw0, db0, dw1, db1, accumulate, (float *)ws,
+                                           (hipStream_t)stream);
+  });
 }
 
 namespace gmz {
@@ -696,91 +689,89 @@ GMZ_EXPORT int gmz_seg_bn_small_workspace_bytes(int nseg, int C, size_t *out) {
   return 0;
 }
 
+// The argument and capacity checks of the four gmz_seg_bn_* entry points.  small: the few-channel variant (C <= 8, with a
+// workspace).  nseg_cap and note are the entry point's own: its bound on the segments and what its "bad arguments"
+// adds (gmz_seg_bn_backward has neither).  stats: f32 (3 nseg C + nseg), what the forward writes (ABI 10)
+static int seg_bn_check(const char *fn, const char *note, bool operands, int nseg, int nseg_cap, int B, int S, int C,
+                        size_t stats_bytes, bool small, size_t ws_bytes) {
+  if (!operands || nseg <= 0 || nseg > nseg_cap || B <= 0 || S <= 0 || C <= 0 || (small && C > SBS_MAXC) ||
+      (size_t)nseg * B * S * C >= (1ull << 31))
+    return fail(std::string(fn) + ": bad arguments" + note);
+  if (stats_bytes < ((size_t)3 * nseg * C + nseg) * sizeof(float))
+    return fail(std::string(fn) + ": stats of " + std::to_string(stats_bytes) + " bytes, needs (3 nseg C + nseg) f32");
+  if (small && ws_bytes < sbs_ws_need(nseg))
+    return fail(std::string(fn) + ": workspace of " + std::to_string(ws_bytes) + " bytes, needs " +
+                std::to_string(sbs_ws_need(nseg)));
+  return 0;
+}
+
+// gmz_seg_bn_forward (one workgroup per channel) and gmz_seg_bn_forward_small (small: (segment, chunk) workgroups, ws)
+static int seg_bn_forward_entry(const char *fn, bool small, int dtype, const void *x, const uint8_t *row_mask, int nseg,
+                                int B, int S, int C, const float *gamma, const float *beta, float eps, float *y,
+                                float *stats, size_t stats_bytes, int update, float momentum, float *running_mean,
+                                float *running_var, int64_t *num_batches, const float *pre_stats, void *ws,
+                                size_t ws_bytes, void *stream) {
+  if (seg_bn_check(fn, small ? " (1 <= nseg <= 32, 1 <= C <= 8)" : " (1 <= nseg <= 32)", x && y && stats && (!small || ws),
+                   nseg, 32, B, S, C, stats_bytes, small, ws_bytes))
+    return -1;
+  if (update && (!running_mean || !running_var)) return fail(std::string(fn) + ": update needs running statistics");
+  hipStream_t s = (hipStream_t)stream;
+  return by_dtype<true>(fn, dtype, [&](auto t) {
+    using T = dtype_of<decltype(t)>;
+    return small ? sbs_fwd<T>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum, running_mean,
+                              running_var, num_batches, pre_stats, (double *)ws, s)
+                 : seg_bn_fwd<T>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum, running_mean,
+                                 running_var, num_batches, pre_stats, s);
+  });
+}
+
+// gmz_seg_bn_backward and gmz_seg_bn_backward_small
+static int seg_bn_backward_entry(const char *fn, bool small, int dtype, const void *x, const float *dy,
+                                 const uint8_t *row_mask, int nseg, int B, int S, int C, const float *gamma,
+                                 const float *stats, size_t stats_bytes, void *dx, float *dgamma, float *dbeta,
+                                 int accumulate, void *ws, size_t ws_bytes, void *stream) {
+  if (seg_bn_check(fn, small ? " (1 <= nseg <= 32, 1 <= C <= 8)" : "", x && dy && stats && dx && (!small || ws), nseg,
+                   small ? 32 : INT_MAX, B, S, C, stats_bytes, small, ws_bytes))
+    return -1;
+  hipStream_t s = (hipStream_t)stream;
+  return by_dtype<true>(fn, dtype, [&](auto t) {
+    using T = dtype_of<decltype(t)>;
+    return small ? sbs_bwd<T>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, (double *)ws, s)
+                 : seg_bn_bwd<T>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, s);
+  });
+}
+
 GMZ_EXPORT int gmz_seg_bn_forward_small(int dtype, const void *x, const uint8_t *row_mask, int nseg, int B, int S, int C,
                                         const float *gamma, const float *beta, float eps, float *y, float *stats,
                                         size_t stats_bytes, int update, float momentum, float *running_mean,
                                         float *running_var, int64_t *num_batches, const float *pre_stats, void *ws,
                                         size_t ws_bytes, void *stream) {
-  if (!x || !y || !stats || !ws || nseg <= 0 || nseg > 32 || B <= 0 || S <= 0 || C <= 0 || C > SBS_MAXC ||
-      (size_t)nseg * B * S * C >= (1ull << 31))
-    return fail("gmz_seg_bn_forward_small: bad arguments (1 <= nseg <= 32, 1 <= C <= 8)");
-  if (stats_bytes < ((size_t)3 * nseg * C + nseg) * sizeof(float))
-    return fail("gmz_seg_bn_forward_small: stats of " + std::to_string(stats_bytes) + " bytes, needs (3 nseg C + nseg) f32");
-  if (ws_bytes < sbs_ws_need(nseg))
-    return fail("gmz_seg_bn_forward_small: workspace of " + std::to_string(ws_bytes) + " bytes, needs " +
-                std::to_string(sbs_ws_need(nseg)));
-  if (update && (!running_mean || !running_var)) return fail("gmz_seg_bn_forward_small: update needs running statistics");
-  hipStream_t s = (hipStream_t)stream;
-  double *w = (double *)ws;
-  switch (dtype) {
-    case 0: return sbs_fwd<float>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum, running_mean,
-                                  running_var, num_batches, pre_stats, w, s);
-    case 1: return sbs_fwd<__half>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum, running_mean,
-                                   running_var, num_batches, pre_stats, w, s);
-    case 2: return sbs_fwd<__hip_bfloat16>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum,
-                                           running_mean, running_var, num_batches, pre_stats, w, s);
-  }
-  return fail("gmz_seg_bn_forward_small: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return seg_bn_forward_entry("gmz_seg_bn_forward_small", true, dtype, x, row_mask, nseg, B, S, C, gamma, beta, eps, y,
+                              stats, stats_bytes, update, momentum, running_mean, running_var, num_batches, pre_stats,
+                              ws, ws_bytes, stream);
 }
 
 GMZ_EXPORT int gmz_seg_bn_backward_small(int dtype, const void *x, const float *dy, const uint8_t *row_mask, int nseg,
                                          int B, int S, int C, const float *gamma, const float *stats, size_t stats_bytes,
                                          void *dx, float *dgamma, float *dbeta, int accumulate, void *ws,
                                          size_t ws_bytes, void *stream) {
-  if (!x || !dy || !stats || !dx || !ws || nseg <= 0 || nseg > 32 || B <= 0 || S <= 0 || C <= 0 || C > SBS_MAXC ||
-      (size_t)nseg * B * S * C >= (1ull << 31))
-    return fail("gmz_seg_bn_backward_small: bad arguments (1 <= nseg <= 32, 1 <= C <= 8)");
-  if (stats_bytes < ((size_t)3 * nseg * C + nseg) * sizeof(float))
-    return fail("gmz_seg_bn_backward_small: stats of " + std::to_string(stats_bytes) + " bytes, needs (3 nseg C + nseg) f32");
-  if (ws_bytes < sbs_ws_need(nseg))
-    return fail("gmz_seg_bn_backward_small: workspace of " + std::to_string(ws_bytes) + " bytes, needs " +
-                std::to_string(sbs_ws_need(nseg)));
-  hipStream_t s = (hipStream_t)stream;
-  double *w = (double *)ws;
-  switch (dtype) {
-    case 0: return sbs_bwd<float>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, w, s);
-    case 1: return sbs_bwd<__half>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, w, s);
-    case 2:
-      return sbs_bwd<__hip_bfloat16>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, w, s);
-  }
-  return fail("gmz_seg_bn_backward_small: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return seg_bn_backward_entry("gmz_seg_bn_backward_small", true, dtype, x, dy, row_mask, nseg, B, S, C, gamma, stats,
+                               stats_bytes, dx, dgamma, dbeta, accumulate, ws, ws_bytes, stream);
 }
 
 GMZ_EXPORT int gmz_seg_bn_forward(int dtype, const void *x, const uint8_t *row_mask, int nseg, int B, int S, int C,
                                   const float *gamma, const float *beta, float eps, float *y, float *stats,
                                   size_t stats_bytes, int update, float momentum, float *running_mean,
                                   float *running_var, int64_t *num_batches, const float *pre_stats, void *stream) {
-  if (!x || !y || !stats || nseg <= 0 || nseg > 32 || B <= 0 || S <= 0 || C <= 0 ||
-      (size_t)nseg * B * S * C >= (1ull << 31))
-    return fail("gmz_seg_bn_forward: bad arguments (1 <= nseg <= 32)");
-  if (stats_bytes < ((size_t)3 * nseg * C + nseg) * sizeof(float))  // what the kernel writes (ABI 10)
-    return fail("gmz_seg_bn_forward: stats of " + std::to_string(stats_bytes) + " bytes, needs (3 nseg C + nseg) f32");
-  if (update && (!running_mean || !running_var)) return fail("gmz_seg_bn_forward: update needs running statistics");
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return seg_bn_fwd<float>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum, running_mean,
-                                     running_var, num_batches, pre_stats, s);
-    case 1: return seg_bn_fwd<__half>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum, running_mean,
-                                      running_var, num_batches, pre_stats, s);
-    case 2: return seg_bn_fwd<__hip_bfloat16>(x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats, update, momentum,
-                                              running_mean, running_var, num_batches, pre_stats, s);
-  }
-  return fail("gmz_seg_bn_forward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return seg_bn_forward_entry("gmz_seg_bn_forward", false, dtype, x, row_mask, nseg, B, S, C, gamma, beta, eps, y, stats,
+                              stats_bytes, update, momentum, running_mean, running_var, num_batches, pre_stats, nullptr,
+                              0, stream);
 }
 
 GMZ_EXPORT int gmz_seg_bn_backward(int dtype, const void *x, const float *dy, const uint8_t *row_mask, int nseg, int B,
                                    int S, int C, const float *gamma, const float *stats, size_t stats_bytes, void *dx,
                                    float *dgamma, float *dbeta, int accumulate, void *stream) {
-  if (!x || !dy || !stats || !dx || nseg <= 0 || B <= 0 || S <= 0 || C <= 0 || (size_t)nseg * B * S * C >= (1ull << 31))
-    return fail("gmz_seg_bn_backward: bad arguments");
-  if (stats_bytes < ((size_t)3 * nseg * C + nseg) * sizeof(float))
-    return fail("gmz_seg_bn_backward: stats of " + std::to_string(stats_bytes) + " bytes, needs (3 nseg C + nseg) f32");
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return seg_bn_bwd<float>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, s);
-    case 1: return seg_bn_bwd<__half>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, s);
-    case 2:
-      return seg_bn_bwd<__hip_bfloat16>(x, dy, row_mask, nseg, B, S, C, gamma, stats, dx, dgamma, dbeta, accumulate, s);
-  }
-  return fail("gmz_seg_bn_backward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return seg_bn_backward_entry("gmz_seg_bn_backward", false, dtype, x, dy, row_mask, nseg, B, S, C, gamma, stats,
+                               stats_bytes, dx, dgamma, dbeta, accumulate, nullptr, 0, stream);
 }
+

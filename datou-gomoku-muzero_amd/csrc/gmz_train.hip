@@ -993,33 +993,42 @@ GMZ_EXPORT int gmz_grad_add_t_cols(int dtype, const void *src, int P, int C, int
   if (!src || !dst || P <= 0 || C <= 0 || O <= 0 || col0 < 0 || ldo < col0 + O || (size_t)P * C * ldo >= (1ull << 31))
     return fail("gmz_grad_add_t: bad arguments");
   if (C > 65535) return fail("gmz_grad_add_t: C must be <= 65535 (grid z)");
-  hipStream_t st = (hipStream_t)stream;
   const dim3 grid((P + GT - 1) / GT, (O + GT - 1) / GT, C);
-  switch (dtype) {
-    case 0:
-      hipLaunchKernelGGL(k_grad_add_t<float>, grid, dim3(256), 0, st, (const float *)src, P, C, O, dst, ldo, col0);
-      break;
-    case 1:
-      hipLaunchKernelGGL(k_grad_add_t<__half>, grid, dim3(256), 0, st, (const __half *)src, P, C, O, dst, ldo, col0);
-      break;
-    case 2:
-      hipLaunchKernelGGL(k_grad_add_t<__hip_bfloat16>, grid, dim3(256), 0, st, (const __hip_bfloat16 *)src, P, C, O,
-                         dst, ldo, col0);
-      break;
-    default: return fail("gmz_grad_add_t: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
-  }
-  GMZ_LAUNCH_CHECK();
-  return 0;
+  return by_dtype<true>("gmz_grad_add_t", dtype, [&](auto t) {
+    using T = dtype_of<decltype(t)>;
+    hipLaunchKernelGGL(k_grad_add_t<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T *)src, P, C, O, dst, ldo, col0);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_grad_add_t(int dtype, const void *src, int P, int C, int O, float *dst, void *stream) {
   return gmz_grad_add_t_cols(dtype, src, P, C, O, O, 0, dst, stream);
 }
 
+// ---------------------------------------------------------------- the BatchNorm entry points
+// Each is: bn_open (shape, layout, operands), its capacity checks (check_parts for statistics partials it reads,
+// check_bn_ws for the workspace it writes; which of the two and in which order is the entry point's own), check_pair
+// where it updates running statistics, then by_dtype into its launcher.  pfx is the name the messages carry, fn the
+// entry point's own name where the two differ (DESIGN.md lists those).
 static int check_layout(int layout, int C) {
   if (layout == 0) return 0;
   if (layout == 1 && C % 2 == 0 && C <= 2 * BN_THREADS) return 0;
   return fail("gmz_bn: layout must be 0 (NCHW) or 1 (NHWC with even C <= 512)");
+}
+
+// shape_ok: what the entry point asks of its shape beyond positive B, C, S and fewer than 2^31 elements (note says so)
+static int bn_open(const char *pfx, const char *note, int layout, int B, int C, int S, bool shape_ok, bool operands) {
+  if (!shape_ok || B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31))
+    return fail(std::string(pfx) + ": bad shape" + note);
+  if (check_layout(layout, C)) return -1;
+  if (!operands) return fail(std::string(pfx) + ": null operand");
+  return 0;
+}
+
+static int check_pair(const char *pfx, const float *running_mean, const float *running_var) {
+  if ((running_mean == nullptr) != (running_var == nullptr)) return fail(std::string(pfx) + ": running stats pair");
+  return 0;
 }
 
 static size_t bn_ws_need(int layout, int B, int C, int S) {
@@ -1051,115 +1060,68 @@ static int check_parts(const char *fn, int C, long ns, size_t bytes) {
   return 0;
 }
 
+// gmz_bn_forward (relu_mask = nullptr) and gmz_bn_forward_m.  relu_mask: uint8 [B*S][C/8], bit j of byte
+// [pixel][c/8] = y > 0, written by the forward and read by the backward instead of re-reading y (ABI 8)
+static int bn_forward_entry(const char *fn, int dtype, int layout, const void *x, const void *res, const uint8_t *mask,
+                            int B, int C, int S, const float *gamma, const float *beta, float eps, float momentum,
+                            float *running_mean, float *running_var, int64_t *num_batches, int relu, void *y,
+                            float *save, void *ws, size_t ws_bytes, uint8_t *relu_mask, void *stream) {
+  const char *pfx = "gmz_bn_forward";
+  if (bn_open(pfx, "", layout, B, C, S, true, x && y && gamma && beta && save && ws)) return -1;
+  if (check_bn_ws(fn, layout, B, C, S, ws_bytes) || check_pair(pfx, running_mean, running_var)) return -1;
+  if (relu_mask && (!relu || layout != 1)) return fail(std::string(fn) + ": relu_mask needs relu and channels-last");
+  return by_dtype<true>(pfx, dtype, [&](auto t) {
+    return bn_forward<dtype_of<decltype(t)>>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
+                                             running_var, num_batches, relu, y, save, ws, (hipStream_t)stream, relu_mask);
+  });
+}
+
 GMZ_EXPORT int gmz_bn_forward(int dtype, int layout, const void *x, const void *res, const uint8_t *mask, int B, int C,
                               int S, const float *gamma, const float *beta, float eps, float momentum,
                               float *running_mean, float *running_var, int64_t *num_batches, int relu, void *y,
                               float *save, void *ws, size_t ws_bytes, void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_forward: bad shape");
-  if (check_layout(layout, C)) return -1;
-  if (!x || !y || !gamma || !beta || !save || !ws) return fail("gmz_bn_forward: null operand");
-  if (check_bn_ws("gmz_bn_forward", layout, B, C, S, ws_bytes)) return -1;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward: running stats pair");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_forward<float>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                     running_var, num_batches, relu, y, save, ws, st);
-    case 1: return bn_forward<__half>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                      running_var, num_batches, relu, y, save, ws, st);
-    case 2: return bn_forward<__hip_bfloat16>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                              running_var, num_batches, relu, y, save, ws, st);
-  }
-  return fail("gmz_bn_forward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return bn_forward_entry("gmz_bn_forward", dtype, layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
+                          running_var, num_batches, relu, y, save, ws, ws_bytes, nullptr, stream);
+}
+
+GMZ_EXPORT int gmz_bn_forward_m(int dtype, int layout, const void *x, const void *res, const uint8_t *mask, int B, int C,
+                                int S, const float *gamma, const float *beta, float eps, float momentum,
+                                float *running_mean, float *running_var, int64_t *num_batches, int relu, void *y,
+                                float *save, void *ws, size_t ws_bytes, uint8_t *relu_mask, void *stream) {
+  return bn_forward_entry("gmz_bn_forward_m", dtype, layout, x, res, mask, B, C, S, gamma, beta, eps, momentum,
+                          running_mean, running_var, num_batches, relu, y, save, ws, ws_bytes, relu_mask, stream);
+}
+
+// gmz_bn_backward_acc (relu_mask = nullptr) and gmz_bn_backward_acc_m
+static int bn_backward_entry(const char *fn, int dtype, int layout, const void *x, const void *y, const void *dy,
+                             const uint8_t *mask, int B, int C, int S, const float *gamma, const float *save, int relu,
+                             void *dx, void *dres, float *dgamma, float *dbeta, void *ws, size_t ws_bytes,
+                             const uint8_t *relu_mask, void *stream, int accumulate) {
+  const char *pfx = "gmz_bn_backward";
+  if (bn_open(pfx, "", layout, B, C, S, true, x && dy && dx && gamma && save && dgamma && dbeta && ws && (!relu || y)))
+    return -1;
+  if (check_bn_ws(fn, layout, B, C, S, ws_bytes)) return -1;
+  if (relu_mask && (!relu || layout != 1)) return fail(std::string(fn) + ": relu_mask needs relu and channels-last");
+  return by_dtype<true>(pfx, dtype, [&](auto t) {
+    return bn_backward<dtype_of<decltype(t)>>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta,
+                                              ws, (hipStream_t)stream, accumulate, relu_mask);
+  });
 }
 
 GMZ_EXPORT int gmz_bn_backward_acc(int dtype, int layout, const void *x, const void *y, const void *dy,
                                    const uint8_t *mask, int B, int C, int S, const float *gamma, const float *save,
                                    int relu, void *dx, void *dres, float *dgamma, float *dbeta, void *ws,
                                    size_t ws_bytes, void *stream, int accumulate) {
-  if (B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_backward: bad shape");
-  if (check_layout(layout, C)) return -1;
-  if (!x || !dy || !dx || !gamma || !save || !dgamma || !dbeta || !ws || (relu && !y))
-    return fail("gmz_bn_backward: null operand");
-  if (check_bn_ws("gmz_bn_backward", layout, B, C, S, ws_bytes)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_backward<float>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta, ws,
-                                      st, accumulate);
-    case 1: return bn_backward<__half>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta,
-                                       ws, st, accumulate);
-    case 2: return bn_backward<__hip_bfloat16>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma,
-                                               dbeta, ws, st, accumulate);
-  }
-  return fail("gmz_bn_backward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
-}
-
-// the same entry points with the ReLU's output mask (relu_mask_dev uint8 [B*S][C/8], bit j of byte [pixel][c/8] =
-// y > 0): written by the forward, read by the backward instead of re-reading y (ABI 8)
-GMZ_EXPORT int gmz_bn_forward_m(int dtype, int layout, const void *x, const void *res, const uint8_t *mask, int B, int C,
-                                int S, const float *gamma, const float *beta, float eps, float momentum,
-                                float *running_mean, float *running_var, int64_t *num_batches, int relu, void *y,
-                                float *save, void *ws, size_t ws_bytes, uint8_t *relu_mask, void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_forward: bad shape");
-  if (check_layout(layout, C)) return -1;
-  if (!x || !y || !gamma || !beta || !save || !ws) return fail("gmz_bn_forward: null operand");
-  if (check_bn_ws("gmz_bn_forward_m", layout, B, C, S, ws_bytes)) return -1;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward: running stats pair");
-  if (relu_mask && (!relu || layout != 1)) return fail("gmz_bn_forward_m: relu_mask needs relu and channels-last");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_forward<float>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                     running_var, num_batches, relu, y, save, ws, st, relu_mask);
-    case 1: return bn_forward<__half>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                      running_var, num_batches, relu, y, save, ws, st, relu_mask);
-    case 2: return bn_forward<__hip_bfloat16>(layout, x, res, mask, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                              running_var, num_batches, relu, y, save, ws, st, relu_mask);
-  }
-  return fail("gmz_bn_forward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return bn_backward_entry("gmz_bn_backward", dtype, layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma,
+                           dbeta, ws, ws_bytes, nullptr, stream, accumulate);
 }
 
 GMZ_EXPORT int gmz_bn_backward_acc_m(int dtype, int layout, const void *x, const void *y, const void *dy,
                                      const uint8_t *mask, int B, int C, int S, const float *gamma, const float *save,
                                      int relu, void *dx, void *dres, float *dgamma, float *dbeta, void *ws,
                                      size_t ws_bytes, const uint8_t *relu_mask, void *stream, int accumulate) {
-  if (B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_backward: bad shape");
-  if (check_layout(layout, C)) return -1;
-  if (!x || !dy || !dx || !gamma || !save || !dgamma || !dbeta || !ws || (relu && !y))
-    return fail("gmz_bn_backward: null operand");
-  if (check_bn_ws("gmz_bn_backward_acc_m", layout, B, C, S, ws_bytes)) return -1;
-  if (relu_mask && (!relu || layout != 1)) return fail("gmz_bn_backward_acc_m: relu_mask needs relu and channels-last");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_backward<float>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta, ws,
-                                      st, accumulate, relu_mask);
-    case 1: return bn_backward<__half>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta,
-                                       ws, st, accumulate, relu_mask);
-    case 2: return bn_backward<__hip_bfloat16>(layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma,
-                                               dbeta, ws, st, accumulate, relu_mask);
-  }
-  return fail("gmz_bn_backward: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
-}
-
-GMZ_EXPORT int gmz_bn_forward_stats_m(int dtype, const void *x, const void *res, int B, int C, int S, const float *gamma,
-                                      const float *beta, float eps, float momentum, float *running_mean,
-                                      float *running_var, int64_t *num_batches, int relu, void *y, float *save,
-                                      const double *stats, int ns, size_t stats_bytes, uint8_t *relu_mask,
-                                      void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || ns <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_forward_stats: bad shape");
-  if (check_layout(1, C)) return -1;
-  if (!x || !y || !gamma || !beta || !save || !stats) return fail("gmz_bn_forward_stats: null operand");
-  if (check_parts("gmz_bn_forward_stats_m", C, ns, stats_bytes)) return -1;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward_stats: running stats pair");
-  if (relu_mask && !relu) return fail("gmz_bn_forward_stats_m: relu_mask needs relu");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_forward_stats<float>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean, running_var,
-                                           num_batches, relu, y, save, stats, ns, st, relu_mask);
-    case 1: return bn_forward_stats<__half>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean, running_var,
-                                            num_batches, relu, y, save, stats, ns, st, relu_mask);
-    case 2: return bn_forward_stats<__hip_bfloat16>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                                    running_var, num_batches, relu, y, save, stats, ns, st, relu_mask);
-  }
-  return fail("gmz_bn_forward_stats: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return bn_backward_entry("gmz_bn_backward_acc_m", dtype, layout, x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres,
+                           dgamma, dbeta, ws, ws_bytes, relu_mask, stream, accumulate);
 }
 
 GMZ_EXPORT int gmz_bn_backward(int dtype, int layout, const void *x, const void *y, const void *dy,
@@ -1170,76 +1132,91 @@ GMZ_EXPORT int gmz_bn_backward(int dtype, int layout, const void *x, const void 
                              ws_bytes, stream, 0);
 }
 
+// gmz_bn_forward_stats (relu_mask = nullptr) and gmz_bn_forward_stats_m
+static int bn_forward_stats_entry(const char *fn, int dtype, const void *x, const void *res, int B, int C, int S,
+                                  const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
+                                  float *running_var, int64_t *num_batches, int relu, void *y, float *save,
+                                  const double *stats, int ns, size_t stats_bytes, uint8_t *relu_mask, void *stream) {
+  const char *pfx = "gmz_bn_forward_stats";
+  if (bn_open(pfx, "", 1, B, C, S, ns > 0, x && y && gamma && beta && save && stats)) return -1;
+  if (check_parts(fn, C, ns, stats_bytes) || check_pair(pfx, running_mean, running_var)) return -1;
+  if (relu_mask && !relu) return fail(std::string(fn) + ": relu_mask needs relu");
+  return by_dtype<true>(pfx, dtype, [&](auto t) {
+    return bn_forward_stats<dtype_of<decltype(t)>>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean, running_var,
+                                                   num_batches, relu, y, save, stats, ns, (hipStream_t)stream, relu_mask);
+  });
+}
+
+GMZ_EXPORT int gmz_bn_forward_stats(int dtype, const void *x, const void *res, int B, int C, int S, const float *gamma,
+                                    const float *beta, float eps, float momentum, float *running_mean,
+                                    float *running_var, int64_t *num_batches, int relu, void *y, float *save,
+                                    const double *stats, int ns, size_t stats_bytes, void *stream) {
+  return bn_forward_stats_entry("gmz_bn_forward_stats", dtype, x, res, B, C, S, gamma, beta, eps, momentum, running_mean,
+                                running_var, num_batches, relu, y, save, stats, ns, stats_bytes, nullptr, stream);
+}
+
+GMZ_EXPORT int gmz_bn_forward_stats_m(int dtype, const void *x, const void *res, int B, int C, int S, const float *gamma,
+                                      const float *beta, float eps, float momentum, float *running_mean,
+                                      float *running_var, int64_t *num_batches, int relu, void *y, float *save,
+                                      const double *stats, int ns, size_t stats_bytes, uint8_t *relu_mask,
+                                      void *stream) {
+  return bn_forward_stats_entry("gmz_bn_forward_stats_m", dtype, x, res, B, C, S, gamma, beta, eps, momentum,
+                                running_mean, running_var, num_batches, relu, y, save, stats, ns, stats_bytes, relu_mask,
+                                stream);
+}
+
 GMZ_EXPORT int gmz_bn_forward_seg(int dtype, const void *x, const void *res, const uint8_t *mask, int B, int nseg, int C,
                                   int S, const float *gamma, const float *beta, float eps, float momentum,
                                   float *running_mean, float *running_var, int64_t *num_batches, int relu, void *y,
                                   float *save, void *ws, size_t ws_bytes, const double *board_stats,
                                   size_t board_stats_bytes, void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || nseg <= 0 || B % nseg || (size_t)B * C * S >= (1ull << 31))
-    return fail("gmz_bn_forward_seg: bad shape (B must be a multiple of nseg)");
-  if (check_layout(1, C)) return -1;
-  if (!x || !y || !gamma || !beta || !save || !ws) return fail("gmz_bn_forward_seg: null operand");
-  if (check_bn_ws("gmz_bn_forward_seg", 1, B, C, S, ws_bytes)) return -1;
+  const char *fn = "gmz_bn_forward_seg";
+  if (bn_open(fn, " (B must be a multiple of nseg)", 1, B, C, S, nseg > 0 && B % nseg == 0,
+              x && y && gamma && beta && save && ws))
+    return -1;
+  if (check_bn_ws(fn, 1, B, C, S, ws_bytes)) return -1;
   if (!board_stats) {  // the reduction pass writes nseg * seg_splits slots: more than the workspace's when segments are tiny
     const size_t need = (size_t)C * nseg * seg_splits(B, nseg, C, S) * 3 * sizeof(double);
     if (ws_bytes < need)
       return fail("gmz_bn_forward_seg: workspace of " + std::to_string(ws_bytes) + " bytes, " + std::to_string(nseg) +
                   " segments of fewer than 16 pixels need " + std::to_string(need) + " (C * nseg * 24)");
   }
-  if (board_stats && check_parts("gmz_bn_forward_seg", C, B, board_stats_bytes)) return -1;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward_seg: running stats pair");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_forward_seg<float>(x, res, mask, B, nseg, C, S, gamma, beta, eps, momentum, running_mean,
-                                         running_var, num_batches, relu, y, save, ws, board_stats, st);
-    case 1: return bn_forward_seg<__half>(x, res, mask, B, nseg, C, S, gamma, beta, eps, momentum, running_mean,
-                                          running_var, num_batches, relu, y, save, ws, board_stats, st);
-    case 2: return bn_forward_seg<__hip_bfloat16>(x, res, mask, B, nseg, C, S, gamma, beta, eps, momentum, running_mean,
-                                                  running_var, num_batches, relu, y, save, ws, board_stats, st);
-  }
-  return fail("gmz_bn_forward_seg: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  if (board_stats && check_parts(fn, C, B, board_stats_bytes)) return -1;
+  if (check_pair(fn, running_mean, running_var)) return -1;
+  return by_dtype<true>(fn, dtype, [&](auto t) {
+    return bn_forward_seg<dtype_of<decltype(t)>>(x, res, mask, B, nseg, C, S, gamma, beta, eps, momentum, running_mean,
+                                                 running_var, num_batches, relu, y, save, ws, board_stats,
+                                                 (hipStream_t)stream);
+  });
 }
 
 GMZ_EXPORT int gmz_bn_eval(int dtype, int layout, const void *x, const void *res, int B, int C, int S,
                            const float *gamma, const float *beta, const float *running_mean,
                            const float *running_var, float eps, int relu, void *y, void *ws, size_t ws_bytes,
                            void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_eval: bad shape");
-  if (check_layout(layout, C)) return -1;
-  if (!x || !y || !gamma || !beta || !running_mean || !running_var || !ws) return fail("gmz_bn_eval: null operand");
-  if (check_bn_ws("gmz_bn_eval", layout, B, C, S, ws_bytes)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_eval<float>(layout, x, res, B, C, S, gamma, beta, running_mean, running_var, eps, relu, y, ws, st);
-    case 1: return bn_eval<__half>(layout, x, res, B, C, S, gamma, beta, running_mean, running_var, eps, relu, y, ws, st);
-    case 2:
-      return bn_eval<__hip_bfloat16>(layout, x, res, B, C, S, gamma, beta, running_mean, running_var, eps, relu, y, ws,
-                                     st);
-  }
-  return fail("gmz_bn_eval: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  const char *fn = "gmz_bn_eval";
+  if (bn_open(fn, "", layout, B, C, S, true, x && y && gamma && beta && running_mean && running_var && ws)) return -1;
+  if (check_bn_ws(fn, layout, B, C, S, ws_bytes)) return -1;
+  return by_dtype<true>(fn, dtype, [&](auto t) {
+    return bn_eval<dtype_of<decltype(t)>>(layout, x, res, B, C, S, gamma, beta, running_mean, running_var, eps, relu, y,
+                                          ws, (hipStream_t)stream);
+  });
 }
 
 GMZ_EXPORT int gmz_bn_backward_stats(int dtype, const void *x, const void *y, const void *dy, const uint8_t *mask,
                                      int B, int C, int S, const float *gamma, const float *save, int relu, void *dx,
                                      void *dres, float *dgamma, float *dbeta, const double *stats, int ns,
                                      size_t stats_bytes, void *ws, size_t ws_bytes, void *stream, int accumulate) {
-  if (B <= 0 || C <= 0 || S <= 0 || ns <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_backward_stats: bad shape");
-  if (check_layout(1, C)) return -1;
-  if (!x || !dy || !dx || !gamma || !save || !dgamma || !dbeta || !stats || !ws || (relu && !y))
-    return fail("gmz_bn_backward_stats: null operand");
-  if (check_parts("gmz_bn_backward_stats", C, ns, stats_bytes) || check_bn_ws("gmz_bn_backward_stats", 1, B, C, S, ws_bytes))
+  const char *fn = "gmz_bn_backward_stats";
+  if (bn_open(fn, "", 1, B, C, S, ns > 0,
+              x && dy && dx && gamma && save && dgamma && dbeta && stats && ws && (!relu || y)))
     return -1;
-  hipStream_t st = (hipStream_t)stream;
+  if (check_parts(fn, C, ns, stats_bytes) || check_bn_ws(fn, 1, B, C, S, ws_bytes)) return -1;
   float *coef = (float *)((double *)ws + ws_doubles(B, C, S, 1));  // where gmz_bn_backward keeps them
-  switch (dtype) {
-    case 0: return bn_backward_stats<float>(x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta, stats,
-                                            ns, coef, st, accumulate);
-    case 1: return bn_backward_stats<__half>(x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta, stats,
-                                             ns, coef, st, accumulate);
-    case 2: return bn_backward_stats<__hip_bfloat16>(x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta,
-                                                     stats, ns, coef, st, accumulate);
-  }
-  return fail("gmz_bn_backward_stats: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  return by_dtype<true>(fn, dtype, [&](auto t) {
+    return bn_backward_stats<dtype_of<decltype(t)>>(x, y, dy, mask, B, C, S, gamma, save, relu, dx, dres, dgamma, dbeta,
+                                                    stats, ns, coef, (hipStream_t)stream, accumulate);
+  });
 }
 
 template <typename T>
@@ -1266,45 +1243,18 @@ GMZ_EXPORT int gmz_bn_forward_deferred(int dtype, const void *x, const uint8_t *
                                        float momentum, float *running_mean, float *running_var, int64_t *num_batches,
                                        float *save, const double *stats, int ns, size_t stats_bytes, void *ws,
                                        size_t ws_bytes, void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_forward_deferred: bad shape");
-  if (check_layout(1, C)) return -1;
-  if (!save || (!stats && (!x || !ws))) return fail("gmz_bn_forward_deferred: null operand");
+  const char *fn = "gmz_bn_forward_deferred";
+  if (bn_open(fn, "", 1, B, C, S, true, save && (stats || (x && ws)))) return -1;
   if (stats) {
     if (ns <= 0) return fail("gmz_bn_forward_deferred: ns must be positive");
-    if (check_parts("gmz_bn_forward_deferred", C, ns, stats_bytes)) return -1;
-  } else if (check_bn_ws("gmz_bn_forward_deferred", 1, B, C, S, ws_bytes)) {
+    if (check_parts(fn, C, ns, stats_bytes)) return -1;
+  } else if (check_bn_ws(fn, 1, B, C, S, ws_bytes)) {
     return -1;
   }
-  if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward_deferred: running stats pair");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_forward_deferred<float>(x, mask, B, C, S, eps, momentum, running_mean, running_var, num_batches,
-                                              save, stats, ns, ws, st);
-    case 1: return bn_forward_deferred<__half>(x, mask, B, C, S, eps, momentum, running_mean, running_var, num_batches,
-                                               save, stats, ns, ws, st);
-    case 2: return bn_forward_deferred<__hip_bfloat16>(x, mask, B, C, S, eps, momentum, running_mean, running_var,
-                                                       num_batches, save, stats, ns, ws, st);
-  }
-  return fail("gmz_bn_forward_deferred: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+  if (check_pair(fn, running_mean, running_var)) return -1;
+  return by_dtype<true>(fn, dtype, [&](auto t) {
+    return bn_forward_deferred<dtype_of<decltype(t)>>(x, mask, B, C, S, eps, momentum, running_mean, running_var,
+                                                      num_batches, save, stats, ns, ws, (hipStream_t)stream);
+  });
 }
 
-GMZ_EXPORT int gmz_bn_forward_stats(int dtype, const void *x, const void *res, int B, int C, int S, const float *gamma,
-                                    const float *beta, float eps, float momentum, float *running_mean,
-                                    float *running_var, int64_t *num_batches, int relu, void *y, float *save,
-                                    const double *stats, int ns, size_t stats_bytes, void *stream) {
-  if (B <= 0 || C <= 0 || S <= 0 || ns <= 0 || (size_t)B * C * S >= (1ull << 31)) return fail("gmz_bn_forward_stats: bad shape");
-  if (check_layout(1, C)) return -1;
-  if (!x || !y || !gamma || !beta || !save || !stats) return fail("gmz_bn_forward_stats: null operand");
-  if (check_parts("gmz_bn_forward_stats", C, ns, stats_bytes)) return -1;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return fail("gmz_bn_forward_stats: running stats pair");
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return bn_forward_stats<float>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean, running_var,
-                                           num_batches, relu, y, save, stats, ns, st);
-    case 1: return bn_forward_stats<__half>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean, running_var,
-                                            num_batches, relu, y, save, stats, ns, st);
-    case 2: return bn_forward_stats<__hip_bfloat16>(x, res, B, C, S, gamma, beta, eps, momentum, running_mean,
-                                                    running_var, num_batches, relu, y, save, stats, ns, st);
-  }
-  return fail("gmz_bn_forward_stats: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
-}
