@@ -876,8 +876,8 @@ __global__ void __launch_bounds__(OPT_THREADS) k_opt_sumsq(const float *__restri
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// pass 2 (one wave): coef = {found_inf (0/1), gradient multiplier = inv_scale * clip}; the Adam step advanced when
-// the step is taken; nonfinite reset for the next step
+// pass 2 (one wave): coef = {skipped (0/1: a non-finite gradient AND skip_on_inf), gradient multiplier =
+// inv_scale * clip}; the Adam step advanced when the step is taken; nonfinite reset for the next step
 __global__ void k_opt_finalize(const double *__restrict__ part, int nb, int *__restrict__ nonfinite,
                                const float *__restrict__ scale, float max_norm, int skip_on_inf, float *__restrict__ coef,
                                float *__restrict__ step) {

@@ -552,8 +552,13 @@ int gmz_grad_add_t_cols(int dtype, const void *src_dev, int P, int C, int O, int
  * target twin or NULL; every element of the bucket in exactly one item, items of at most `chunk` elements.
  * scale: the GradScaler's scale (device f32, NULL = 1); skip_on_inf: a non-finite gradient skips Adam (the target
  * update and the gradient zeroing still run).  lr, step: device f32 scalars (step advanced on the device when the
- * step is taken); coef: device f32 [2] = {found_inf, inv_scale * clip} written for the GradScaler's update.
- * workspace: gmz_opt_layout's bytes, zero-filled once.  The gradient is zeroed for the next step.  (Round 6, additive) */
+ * step is taken); coef: device f32 [2] = {skipped, inv_scale * clip} written for the GradScaler's update.
+ * workspace: gmz_opt_layout's bytes, zero-filled once.  The gradient is zeroed for the next step.  (Round 6, additive)
+ * The bucket holds the SCALED gradient.  norm = sqrt(sum g^2) / scale, the norm of the unscaled gradient;
+ * clip = min(max_norm / (norm + 1e-6), 1), as clip_grad_norm_; each element's gradient is g * coef[1] + weight_decay * p
+ * with coef[1] = clip / scale.  coef[0] = 1 when the step was skipped (a non-finite gradient AND skip_on_inf), else 0;
+ * on a skipped step coef[1] is still written but comes from a non-finite norm and means nothing.  The bias
+ * corrections 1 - beta^step use the advanced step; the target update reads the parameter just updated. */
 int gmz_opt_layout(size_t *item_bytes, int *chunk, size_t *workspace_bytes);
 int gmz_opt_step(const void *items_dev, int n_items, float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev,
                  long long n, const float *scale_dev, int skip_on_inf, float max_norm, const float *lr_dev, float beta1,
@@ -583,7 +588,11 @@ int gmz_head_conv1x1_forward(int dtype, const void *x_dev, long P, int C, const 
  * [3*nseg*C + nseg]: per segment and channel mean, invstd, unbiased variance, then per segment the live-row count.
  * update != 0: running_mean/var_dev (f32 [C]) and num_batches_dev (int64) updated segment after segment, a segment
  * without live rows skipped; pre_stats_dev (or NULL): an earlier call's stats of the same nseg segments whose update
- * goes first in each segment (the projection's dynamics step s, then target s).  1 <= nseg <= 32.  (ABI 9) */
+ * goes first in each segment (the projection's dynamics step s, then target s).  1 <= nseg <= 32.  (ABI 9)
+ * A segment without live rows has mean 0, variance 0 and invstd = 1 / sqrt(eps); its rows are still normalised with
+ * those (and its backward is dx = gamma invstd dy).  A segment with one live row and S = 1 (n = 1) puts its biased
+ * variance into stats and into the running update: there is no n / (n - 1).  A pre_stats segment is applied when ITS
+ * live-row count is > 0, whatever this call's; num_batches counts the updates made, from either source. */
 int gmz_seg_bn_forward(int dtype, const void *x_dev, const uint8_t *row_mask_dev, int nseg, int B, int S, int C,
                        const float *gamma_dev, const float *beta_dev, float eps, float *y_dev, float *stats_dev,
                        size_t stats_bytes, int update, float momentum, float *running_mean_dev, float *running_var_dev,
