@@ -26,7 +26,10 @@ own share of the work, time-sliced on its GPU:
               max (all-reduce MAX), the admission priority kept global (all-reduce MAX);
   weight push every ``model_update_interval`` trainer steps rank 0's weights are broadcast (one flat
               fp32 bucket, weight_sync.broadcast_state_dict) and every rank hot-swaps them into its
-              inference network, as the inference server does on ModelWeightsUpdate.
+              inference network, as the inference server does on ModelWeightsUpdate; ``device_weights=True``
+              (one rank): the trainer's live parameters are folded and packed into the inference networks'
+              buffers by three HIP launches (gmz_net_pack, bit-identical), ordered by stream events, with no
+              host wait and no host copy.
 
 One *iteration* = ``moves_per_iter`` self-play moves of all G games, then ``train_steps_per_iter``
 trainer steps (all ranks together, once every shard holds a batch).  ``concurrent=True`` (GPU): the
@@ -105,6 +108,10 @@ class SelfPlay:
     def load_weights(self, sd):
         self.net.load_state_dict(sd)
 
+    def load_device_weights(self, sd):
+        """Device tensors (Trainer.device_state_dict) packed in place on the current stream, no host copy."""
+        self.net.load_device_state_dict(sd)
+
     def close(self):
         self.eng.close()
 
@@ -114,7 +121,8 @@ class C4Loop:
 
     def __init__(self, selfplay, trainer, buffer, cfg, batch_size, dist=None, moves_per_iter=1,
                  train_steps_per_iter=1, model_update_interval=1000, seed=0, device="cuda", concurrent=False,
-                 device_ingest=False, device_batches=False, reanalyser=None, reanalyse_per_iter=0):
+                 device_ingest=False, device_batches=False, reanalyser=None, reanalyse_per_iter=0,
+                 device_weights=False):
         self.sp, self.tr, self.rb, self.cfg = selfplay, trainer, buffer, cfg
         self.B, self.dist = int(batch_size), dist
         self.moves_per_iter, self.train_steps_per_iter = int(moves_per_iter), int(train_steps_per_iter)
@@ -164,6 +172,19 @@ class C4Loop:
                 raise ValueError("device_batches: the trainer steps on its PHYSICAL_BATCH_SIZE, not on a batch of %d"
                                  % self.B)
 
+        # device_weights: a push packs the trainer's live parameters into the inference networks in HIP
+        # (GomokuNetHip.load_device_state_dict), ordered between the two streams by events; off = the host path
+        self.device_weights = bool(device_weights)
+        if self.device_weights:
+            if self.device.type != "cuda":
+                raise ValueError("device_weights needs the loop on a GPU")
+            if self.world > 1:
+                # BatchNorm running statistics differ per rank, so rank 0's would still have to be broadcast
+                raise ValueError("device_weights: a multi-rank push stays on the host path (world = %d)" % self.world)
+            if not hasattr(trainer, "device_state_dict") or not hasattr(selfplay, "load_device_weights"):
+                raise ValueError("device_weights needs Trainer.device_state_dict and a self-play source with "
+                                 "load_device_weights (loop.SelfPlay)")
+
     # ---------------------------------------------------------------- pieces
     def _add_games(self, done):
         c = self.cfg
@@ -190,6 +211,8 @@ class C4Loop:
 
     def push_weights(self):
         """ModelWeightsUpdate (workers.py:587-593): rank 0's trainer weights -> every rank's inference net."""
+        if self.device_weights:
+            return self._push_device_weights()
         if self.train_stream is not None:
             self.train_stream.synchronize()  # the step that made these weights has finished
         sd = self.tr.state_dict_cpu()
@@ -213,6 +236,29 @@ class C4Loop:
             self.sp.load_weights(sd)
             if self.ra is not None:
                 self.ra.load_weights(sd)
+        self.weight_pushes += 1
+
+    def _push_device_weights(self):
+        """The push with no host wait and no host copy: the self-play stream waits for the step that made the weights
+        (an event on the stream that step was enqueued on: the train stream in concurrent mode), packs them into
+        self-play's network and the re-analyser's, and the trainer's stream waits for the packs before its next step
+        may overwrite the parameters they read."""
+        cur = torch.cuda.current_stream(self.device)
+        sd = self.tr.device_state_dict()
+        two = cur != self.sp_stream
+        if two:
+            made = torch.cuda.Event()
+            made.record(cur)
+            self.sp_stream.wait_event(made)
+        with torch.cuda.stream(self.sp_stream):
+            self.sp.load_device_weights(sd)
+            if self.ra is not None:
+                self.ra.load_device_weights(sd)
+            if two:
+                packed = torch.cuda.Event()
+                packed.record(self.sp_stream)
+        if two:
+            cur.wait_event(packed)
         self.weight_pushes += 1
 
     def train_step(self):
@@ -315,7 +361,7 @@ def run_c4(args, rank, world, dist, backend, log=print):
                   concurrent=getattr(args, "loop_concurrent", False),
                   device_ingest=getattr(args, "loop_device_ingest", False),
                   device_batches=getattr(args, "loop_device_batches", False), reanalyser=ra,
-                  reanalyse_per_iter=ra_passes)
+                  reanalyse_per_iter=ra_passes, device_weights=getattr(args, "loop_device_weights", False))
     t_w = time.perf_counter()
     loop.run(args.loop_warmup)
     torch.cuda.synchronize()

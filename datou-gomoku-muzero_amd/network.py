@@ -57,6 +57,8 @@ _lib.register({
     "gmz_net_recurrent": ([ctypes.POINTER(NetWeights), P, P, P, P, I, P, P, P, P, SZ, P], I),
     "gmz_net_recurrent_tower": ([ctypes.POINTER(NetWeights), P, P, P, P, I, P, SZ, P], I),
     "gmz_net_recurrent_heads": ([ctypes.POINTER(NetWeights), P, P, I, P, P, P, P, SZ, P], I),
+    "gmz_net_pack_job_bytes": ([I, ctypes.POINTER(SZ)], I),
+    "gmz_net_pack": ([ctypes.POINTER(NetWeights), P, SZ, P], I),
 })
 
 
@@ -191,6 +193,38 @@ def pack_weights(sd, cfg, precision="fp16"):
     return out
 
 
+def device_pack_sources(cfg):
+    """[(reference key, shape)] of the tensors ``pack_weights`` reads, in the order of gmz_net_pack's job table
+    (include/gmz.h): 2 + 4 * blocks conv groups (weight, then the BatchNorm's weight, bias, running_mean, running_var),
+    then 23 single tensors."""
+    A, nb, hd = cfg.BOARD_SIZE * cfg.BOARD_SIZE, cfg.NUM_RES_BLOCKS, cfg.HEAD_HIDDEN_DIM
+    out = []
+
+    def bn(p, n):
+        return [(p + k, (n,)) for k in (".weight", ".bias", ".running_mean", ".running_var")]
+
+    def tower(prefix):
+        for i in range(nb):
+            for k in (1, 2):
+                p = "%s.resblocks.%d." % (prefix, i)
+                out.extend([(p + "conv%d.weight" % k, (C, C, 3, 3))] + bn(p + "bn%d" % k, C))
+
+    out += [("representation_net.conv.weight", (C, 3, 3, 3))] + bn("representation_net.bn", C)
+    tower("representation_net")
+    out += [("dynamics_net.conv.weight", (C, C + 16, 3, 3))] + bn("dynamics_net.bn", C)
+    tower("dynamics_net")
+    P_ = "prediction_net."
+    out += [("dynamics_net.action_embed_conv.weight", (16, 1, 1, 1))]
+    out += [(P_ + "policy_conv.weight", (2, C, 1, 1)), (P_ + "policy_conv.bias", (2,))] + bn(P_ + "policy_bn", 2)
+    out += [(P_ + "value_conv.weight", (1, C, 1, 1)), (P_ + "value_conv.bias", (1,))] + bn(P_ + "value_bn", 1)
+    out += [(P_ + "policy_fc.weight", (A, 2 * A)), (P_ + "policy_fc.bias", (A,)),
+            (P_ + "value_fc1.weight", (hd, A)), (P_ + "value_fc1.bias", (hd,)),
+            (P_ + "value_fc2.weight", (3, hd)), (P_ + "value_fc2.bias", (3,)),
+            ("dynamics_net.reward_fc.0.weight", (hd, C * A)), ("dynamics_net.reward_fc.0.bias", (hd,)),
+            ("dynamics_net.reward_fc.2.weight", (3, hd)), ("dynamics_net.reward_fc.2.bias", (3,))]
+    return out
+
+
 class KernelTimer:
     """HIP-event pairs recorded on the launch stream around one kernel; read after a sync."""
 
@@ -270,6 +304,47 @@ class GomokuNetHip:
             q.w = NetWeights.from_buffer_copy(w)
             q.w.max_grid = keep
             q._tensors = self._tensors
+
+    def load_device_state_dict(self, sd):
+        """:meth:`load_state_dict` without the host: ``sd`` maps the reference key names to float32 tensors on this
+        network's device, of any strides (Trainer.device_state_dict: the live parameters, channels-last on the GPU);
+        ``num_batches_tracked`` and keys ``pack_weights`` does not read are ignored.  gmz_net_pack folds, permutes and
+        rounds them INTO the packed tensors on the current stream (three launches, bit for bit ``pack_weights``): every
+        packed tensor, ``self.w`` and the split() children keep their pointers.  The job table (pointers and strides,
+        include/gmz.h) is built and uploaded on first use and reused while the sources' pointers and strides are
+        unchanged, so a repeated push neither allocates nor copies and can be captured into a graph; the sources are
+        kept referenced meanwhile.  Successive pushes belong on one stream (a rebuilt table overwrites the old one in
+        stream order).  Raises ValueError for a missing key, a tensor that is not float32, not on this device or of the
+        wrong shape."""
+        dev = self.pool.device
+        srcs, key = [], []
+        for k, shape in device_pack_sources(self.cfg):
+            t = sd.get(k) if hasattr(sd, "get") else None
+            if t is None:
+                raise ValueError("load_device_state_dict: missing key %r" % k)
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError("load_device_state_dict: %r must be a CUDA tensor (load_state_dict takes host weights)" % k)
+            if t.device != dev:
+                raise ValueError("load_device_state_dict: %r is on %s, the network on %s" % (k, t.device, dev))
+            if t.dtype != torch.float32:
+                raise ValueError("load_device_state_dict: %r must be float32, not %s" % (k, t.dtype))
+            if tuple(t.shape) != shape:
+                raise ValueError("load_device_state_dict: %r has shape %s, expected %s" % (k, tuple(t.shape), shape))
+            srcs.append(t)
+            key.append((t.data_ptr(),) + tuple(t.stride()))
+        nbytes = _lib.query("gmz_net_pack_job_bytes", self.cfg.NUM_RES_BLOCKS)
+        if nbytes != 40 * len(srcs):
+            raise _lib.GmzError("gmz_net_pack_job_bytes: %d, expected %d" % (nbytes, 40 * len(srcs)))
+        if getattr(self, "_pack_key", None) != key:
+            table = np.zeros((len(srcs), 5), np.int64)  # {pointer, strides[4] in elements}
+            for row, k in zip(table, key):
+                row[:len(k)] = k
+            if getattr(self, "_pack_jobs", None) is None:
+                self._pack_jobs = torch.empty(len(srcs), 5, dtype=torch.int64, device=dev)
+            self._pack_jobs.copy_(torch.from_numpy(table))
+            self._pack_key, self._pack_srcs = key, srcs
+        with torch.cuda.device(dev):
+            check(self.lib.gmz_net_pack(ctypes.byref(self.w), ptr(self._pack_jobs), nbytes, _lib.stream_ptr()))
 
     def ensure_slots(self, n, stream=None):
         """At least ``n`` hidden-state slots in ``self.pool`` (engine._place_hidden, between moves: the

@@ -186,6 +186,11 @@ class RingReanalyser:
         if self.net is not None:
             self.net.load_state_dict(sd)
 
+    def load_device_weights(self, sd):
+        """Device tensors (Trainer.device_state_dict) packed in place on the current stream, no host copy."""
+        if self.net is not None:
+            self.net.load_device_state_dict(sd)
+
     def close(self):
         self.eng.close()
 

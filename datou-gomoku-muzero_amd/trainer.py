@@ -2508,3 +2508,9 @@ class Trainer:
     def state_dict_cpu(self):
         """ModelWeightsUpdate payload (workers.py:587-593) for the self-play engines."""
         return {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
+
+    def device_state_dict(self):
+        """The live model's parameters and buffers under the reference's key names, on the trainer's device and with
+        no copy (GomokuNetHip.load_device_state_dict reads them where they are: the next optimiser step overwrites
+        them, so a reader on another stream is ordered before it by the caller, loop.C4Loop.push_weights)."""
+        return {k: v.detach() for k, v in self.model.state_dict().items()}

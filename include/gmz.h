@@ -326,6 +326,39 @@ int gmz_net_recurrent_heads(const gmz_net_weights *w, const uint16_t *hid_pool_d
                             int rows, float *logits_dev, float *value_dev, float *reward_dev, void *workspace_dev,
                             size_t workspace_bytes, void *stream);
 
+/* network.py:pack_weights on the device: the float32 tensors of a reference state_dict that live in device memory
+ * (the trainer's parameters and BatchNorm buffers) are folded, permuted and rounded INTO the 19 buffers `dst` points
+ * to, bit for bit what pack_weights computes on the host (eval-mode BatchNorm eps 1e-4 folded with correctly rounded
+ * float32 operations and no fused multiply-add; fp16 clamped to +-65504 then rounded to nearest even with subnormals
+ * kept, bf16 rounded to nearest even; the zero padding of policy_fc_w and value_fc1_w is written, so the buffers may
+ * hold anything before the call).  The buffers are those of an existing gmz_net_weights of the same board_size,
+ * blocks and dtype (sizes as documented in the struct); the sources must not overlap them and are only read.
+ *
+ * jobs_dev: a device table of gmz_net_pack_job_bytes(blocks) bytes, one 40-byte entry per source tensor:
+ *     struct { const float *ptr; int64_t stride[4]; }     strides in ELEMENTS, one per dimension of the tensor, 0 for
+ *                                                         the dimensions it lacks (any strides: a plain state_dict
+ *                                                         is [o][c][ky][kx] in memory, a channels_last model
+ *                                                         [o][ky][kx][c]; both are read in memory order)
+ * in this order (reference key names; "bn" stands for its .weight, .bias, .running_mean, .running_var, four entries;
+ * B = blocks, i = 0..B-1, so 33 + 20 B entries):
+ *     conv groups, 5 entries each (the conv's .weight, then its bn):
+ *       representation_net.conv / .bn
+ *       representation_net.resblocks.i.conv1 / .bn1, .conv2 / .bn2          (2 B groups, i ascending)
+ *       dynamics_net.conv / .bn
+ *       dynamics_net.resblocks.i.conv1 / .bn1, .conv2 / .bn2                (2 B groups)
+ *     then 23 single tensors:
+ *       dynamics_net.action_embed_conv.weight
+ *       prediction_net.policy_conv.weight, policy_conv.bias, policy_bn (4)
+ *       prediction_net.value_conv.weight, value_conv.bias, value_bn (4)
+ *       prediction_net.policy_fc.weight, policy_fc.bias, value_fc1.weight, value_fc1.bias, value_fc2.weight, value_fc2.bias
+ *       dynamics_net.reward_fc.0.weight, reward_fc.0.bias, reward_fc.2.weight, reward_fc.2.bias
+ * Stream-ordered: three launches on `stream`, no allocation and no host synchronisation, so a call can be captured
+ * into a HIP graph (the table is read at replay: it must stay where it is).  Everything the host can see is checked
+ * before the first launch (null or misaligned destinations, channels, head_hidden, blocks, board_size, dtype,
+ * jobs_bytes); the table's contents cannot be, and a wrong pointer or stride in it is the caller's fault. */
+int gmz_net_pack_job_bytes(int blocks, size_t *out);
+int gmz_net_pack(const gmz_net_weights *dst, const void *jobs_dev, size_t jobs_bytes, void *stream);
+
 /* ------------------------------------------------------------------ trainer kernels (trainer.py) */
 /* Row-masked BatchNorm with the residual add and ReLU fused (training mode), replacing the
  * reference's BatchNorm over the sub-batch of games still in progress (loss.py:89-107, network.py
