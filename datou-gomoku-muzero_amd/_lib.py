@@ -60,6 +60,8 @@ _SIGS = {
     "gmz_engine_errors_async": ([P, P, P], I),
     "gmz_engine_set_active": ([P, P, P], I),
     "gmz_engine_set_simulations": ([P, I], I),
+    "gmz_engine_set_budgets": ([P, P, SZ, P], I),
+    "gmz_engine_waves_for_budgets": ([ctypes.POINTER(EngineCfg), P, P, I, P, P], I),
     "gmz_engine_play_refill": ([P, P, P, P, P, P, P, I, P, I, P, P, P, P, I, P, P, P, I, I, P, P], I),
     "gmz_replay_ingest": ([I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, P, SZ, P, P, P], I),
     "gmz_replay_positions": ([I, I, I, P, SZ, P, I, P, SZ, I, P, SZ, P, SZ, P, SZ, P, SZ, P], I),

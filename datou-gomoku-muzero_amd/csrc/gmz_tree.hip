@@ -58,8 +58,10 @@ struct GameState {
   int32_t depth, k, leaf, n_legal;
   float root_w, mm_max, mm_min, pad0;
   double used;
-  int32_t pad1[2];
+  int32_t n_sims;  // the game's simulation budget for this search (k_begin_move: budget[g], else D.n_sims)
+  int32_t pad1;
 };
+static_assert(sizeof(GameState) == 80, "GameState: 80 bytes (the budget took a padding word)");
 
 // a wave's GameState in SGPRs: the struct is loaded with vector loads (the kernels also store it, so the
 // compiler may not use the scalar cache) and would otherwise stay in 16 VGPRs across the descent
@@ -83,7 +85,8 @@ __device__ __forceinline__ GameState uniform_state(const GameState &v) {
   s.pad0 = 0.f;
   s.used = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v.used)),
                             __builtin_amdgcn_readfirstlane(__double2loint(v.used)));
-  s.pad1[0] = s.pad1[1] = 0;
+  s.n_sims = __builtin_amdgcn_readfirstlane(v.n_sims);
+  s.pad1 = 0;
   return s;
 }
 
@@ -921,7 +924,8 @@ __device__ __forceinline__ double gumbel_noise(uint64_t seed, uint32_t counter, 
 template <int NJ>
 __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restrict__ gumbel_in, uint64_t seed,
                                                     uint32_t counter, float *__restrict__ obs,
-                                                    const uint8_t *__restrict__ active) {
+                                                    const uint8_t *__restrict__ active,
+                                                    const int32_t *__restrict__ budget) {
   __shared__ int16_t table[4][2048];
   __shared__ int16_t oldk[4][512];
   const int w = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
@@ -1021,7 +1025,15 @@ __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restr
     st.next_phase = 0; st.root_n = 0; st.n_sel = 0; st.active = 0;
     st.depth = 0; st.k = 0; st.leaf = -1; st.n_legal = nl;
     st.root_w = 0.f; st.mm_max = -INFINITY; st.mm_min = INFINITY; st.pad0 = 0.f;
-    st.used = 0.0; st.pad1[0] = st.pad1[1] = 0;
+    st.used = 0.0; st.pad1 = 0;
+    // the game's budget (gmz_engine_set_budgets), else the engine's; a value outside [1, D.n_sims] is
+    // clamped into it and raises error bit 1 (the node slots are sized by the creation budget)
+    int ns = budget ? budget[g] : D.n_sims;
+    if (ns < 1 || ns > D.n_sims) {
+      atomicOr(D.err, 2);
+      ns = ns < 1 ? 1 : D.n_sims;
+    }
+    st.n_sims = ns;
     D.gs[g] = st;
     D.node_parent[(size_t)g * D.S] = -1;
     D.node_action[(size_t)g * D.S] = -1;
@@ -1031,7 +1043,7 @@ __global__ void __launch_bounds__(256) k_begin_move(Dev D, const double *__restr
 
 // schedule (mcts.py:158-164)
 __device__ void schedule_init(const Dev &D, GameState &st) {
-  const int n = D.n_sims, m = D.m_top;
+  const int n = st.n_sims, m = D.m_top;
   st.phase = 0; st.m_cur = m; st.used = 0.0;
   if (m <= 1 || log2((double)m) <= 0) st.next_phase = n;
   else {
@@ -1045,7 +1057,7 @@ __device__ int ready_next_phase(const Dev &D, GameState &st) {
   st.phase += 1;
   st.m_cur /= 2;
   if (st.m_cur < 1) return 0;
-  const int n = D.n_sims, m = D.m_top, cm = st.m_cur;
+  const int n = st.n_sims, m = D.m_top, cm = st.m_cur;
   double extra;
   if (cm <= 1 || log2((double)m) <= 0) extra = (double)n - st.used;
   else extra = floor((double)n / (log2((double)m) * cm)) * cm;
@@ -1100,7 +1112,7 @@ __global__ void __launch_bounds__(256) k_set_root(Dev D, const float *__restrict
     if (lane == 0) D.sel[g * MAX_TOP + r] = ba;
   }
   st.n_sel = k;
-  st.active = (st.n_legal > 0 && st.sim < D.n_sims) ? 1 : 0;
+  st.active = (st.n_legal > 0 && st.sim < st.n_sims) ? 1 : 0;
   if (lane == 0) D.gs[g] = st;
 }
 
@@ -1422,7 +1434,7 @@ __device__ __forceinline__ void expand_backup_game(const Dev &D, int g, int lane
     if (lane < ks && rank < keep) D.sel[g * MAX_TOP + rank] = ai;
     st.n_sel = keep;
   }
-  if (st.sim >= D.n_sims) st.active = 0;
+  if (st.sim >= st.n_sims) st.active = 0;
   if (lane == 0) D.gs[g] = st;
 }
 
@@ -1952,6 +1964,8 @@ struct gmz_engine {
   int es_waves;  // resident waves of the engine's k_expand_select variant (0: not measured yet)
   uint8_t *active_buf;    // [G] storage of the active mask (gmz_engine_set_active, gmz_engine_play_refill)
   const uint8_t *active;  // active_buf once a mask is set, nullptr = every game is searched (k_begin_move)
+  int32_t *budget_buf;    // [G] storage of the per-game simulation budgets (gmz_engine_set_budgets)
+  const int32_t *budget;  // budget_buf once budgets are set, nullptr = every game searches D.n_sims (k_begin_move)
   void *bufs[32];
   int nbufs;
 };
@@ -2020,6 +2034,7 @@ GMZ_EXPORT int gmz_engine_create(const gmz_engine_cfg *cfg, gmz_engine **out) {
   rc |= dalloc(e, &D.last_moves, G);
   rc |= dalloc(e, &D.move_counts, G);
   rc |= dalloc(e, &e->active_buf, G);
+  rc |= dalloc(e, &e->budget_buf, G);
   if (rc) {
     gmz_engine_destroy(e);
     return -1;
@@ -2183,7 +2198,7 @@ static int launch_expand_select_nj(gmz_engine *e, hipStream_t s, const float *lo
 GMZ_EXPORT int gmz_engine_begin_move(gmz_engine *e, const double *gumbel, uint64_t seed, float *obs, void *stream) {
   if (!e || !obs) return fail("gmz_engine_begin_move: null argument");
   const uint32_t ctr = e->counter++;
-  GMZ_LAUNCH_NJ(k_begin_move, e, stream, e->D, gumbel, seed, ctr, obs, e->active);
+  GMZ_LAUNCH_NJ(k_begin_move, e, stream, e->D, gumbel, seed, ctr, obs, e->active, e->budget);
   return 0;
 }
 
@@ -2242,36 +2257,60 @@ GMZ_EXPORT int gmz_engine_pending_waves(gmz_engine *e, int32_t *out) {
   return 0;
 }
 
-GMZ_EXPORT int gmz_engine_waves_for_legal(const gmz_engine_cfg *cfg, const int32_t *n_legal, int G, int32_t *out) {
-  if (!cfg || !n_legal || !out) return fail("null argument");
-  const int n = cfg->num_simulations, m = cfg->num_top_actions;
-  int best = 0;
-  for (int g = 0; g < G; ++g) {
-    const int L = n_legal[g];
-    if (L <= 0) continue;
-    // replay of the per-game schedule: k = len(selected) per wave (mcts.py:326), 1 for AlphaZero
-    int sim = 1, waves = 0, ksel = L < m ? L : m, mcur = m, next;
-    double used = 0.0;
-    if (m <= 1 || log2((double)m) <= 0) next = n;
-    else { double x = floor((double)n / (log2((double)m) * m)) * m; next = (int)(x < n ? x : n); }
-    while (sim < n) {
-      sim += cfg->mode == 1 ? ksel : 1;
-      waves++;
-      if (sim >= next) {
-        mcur /= 2;
-        if (mcur >= 1) {
-          double extra = (mcur <= 1 || log2((double)m) <= 0) ? (double)n - used
-                                                              : floor((double)n / (log2((double)m) * mcur)) * mcur;
-          used += extra;
-          long long nx = (long long)next + (long long)extra;
-          next = (int)(nx < n ? nx : n);
-          ksel = ksel < mcur ? ksel : mcur;
-        }
+// host replay of one game's schedule: the waves a search of n simulations takes with L legal moves at the root;
+// k = len(selected) per wave (mcts.py:326), 1 for AlphaZero
+static int schedule_waves(int n, int m, int mode, int L) {
+  if (L <= 0) return 0;
+  int sim = 1, waves = 0, ksel = L < m ? L : m, mcur = m, next;
+  double used = 0.0;
+  if (m <= 1 || log2((double)m) <= 0) next = n;
+  else { double x = floor((double)n / (log2((double)m) * m)) * m; next = (int)(x < n ? x : n); }
+  while (sim < n) {
+    sim += mode == 1 ? ksel : 1;
+    waves++;
+    if (sim >= next) {
+      mcur /= 2;
+      if (mcur >= 1) {
+        double extra = (mcur <= 1 || log2((double)m) <= 0) ? (double)n - used
+                                                            : floor((double)n / (log2((double)m) * mcur)) * mcur;
+        used += extra;
+        long long nx = (long long)next + (long long)extra;
+        next = (int)(nx < n ? nx : n);
+        ksel = ksel < mcur ? ksel : mcur;
       }
     }
+  }
+  return waves;
+}
+
+GMZ_EXPORT int gmz_engine_waves_for_legal(const gmz_engine_cfg *cfg, const int32_t *n_legal, int G, int32_t *out) {
+  if (!cfg || !n_legal || !out) return fail("null argument");
+  int best = 0;
+  for (int g = 0; g < G; ++g) {
+    const int waves = schedule_waves(cfg->num_simulations, cfg->num_top_actions, cfg->mode, n_legal[g]);
     if (waves > best) best = waves;
   }
   *out = best;
+  return 0;
+}
+
+GMZ_EXPORT int gmz_engine_waves_for_budgets(const gmz_engine_cfg *cfg, const int32_t *n_legal, const int32_t *budget,
+                                            int G, int32_t *out_max, int32_t *out_per_game) {
+  if (!cfg || !n_legal || !out_max) return fail("gmz_engine_waves_for_budgets: null argument");
+  if (G < 0) return fail("gmz_engine_waves_for_budgets: G must be >= 0");
+  if (budget)
+    for (int g = 0; g < G; ++g)
+      if (budget[g] < 1 || budget[g] > cfg->num_simulations)
+        return fail("gmz_engine_waves_for_budgets: budget[" + std::to_string(g) + "] = " + std::to_string(budget[g]) +
+                    " is outside [1, " + std::to_string(cfg->num_simulations) + "]");
+  int best = 0;
+  for (int g = 0; g < G; ++g) {
+    const int n = budget ? budget[g] : cfg->num_simulations;
+    const int waves = schedule_waves(n, cfg->num_top_actions, cfg->mode, n_legal[g]);
+    if (out_per_game) out_per_game[g] = waves;
+    if (waves > best) best = waves;
+  }
+  *out_max = best;
   return 0;
 }
 
@@ -2297,6 +2336,24 @@ GMZ_EXPORT int gmz_engine_set_active(gmz_engine *e, const uint8_t *mask_dev, voi
   }
   GMZ_HIP(hipMemcpyAsync(e->active_buf, mask_dev, (size_t)e->D.G, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   e->active = e->active_buf;
+  return 0;
+}
+
+GMZ_EXPORT int gmz_engine_set_budgets(gmz_engine *e, const int32_t *budget_dev, size_t budget_bytes, void *stream) {
+  if (!e) return fail("gmz_engine_set_budgets: null engine");
+  if (!budget_dev) {
+    if (budget_bytes != 0) return fail("gmz_engine_set_budgets: a NULL budget array takes budget_bytes = 0");
+    e->budget = nullptr;
+    return 0;
+  }
+  // (no G divides these: refused whatever the handle, before the engine is read)
+  if (budget_bytes == 0 || budget_bytes % sizeof(int32_t) != 0)
+    return fail("gmz_engine_set_budgets: budget holds " + std::to_string(budget_bytes) + " bytes, not 4 * G");
+  if (budget_bytes !=(size_t)e->D.G * sizeof(int32_t))
+    return fail("gmz_engine_set_budgets: budget holds " + std::to_string(budget_bytes) + " bytes, 4 * G = " +
+                std::to_string((size_t)e->D.G * sizeof(int32_t)));
+  GMZ_HIP(hipMemcpyAsync(e->budget_buf, budget_dev, budget_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  e->budget = e->budget_buf;
   return 0;
 }
 

@@ -138,6 +138,10 @@ class BatchedSelfPlayEngine:
         self._status_event = None
         self._n_legal = np.full(G, A, dtype=np.int32)
         self._active = None  # host copy of set_active's mask (None: every game is searched)
+        self._budgets = None  # host copy of set_budgets' simulations per game (None: every game the engine's)
+        self._bud_dev = None  # its device copy and the pinned staging pair of the uploads (made at the first call)
+        self._bud_host = self._bud_events = None
+        self._bud_flip = 0
         self._refill = None  # play_refill's slot arrays and pinned read-back buffers (arena)
         self._refill_pending = False
         self.finished_seen = 0  # the match's finished-games counter as of the last status read (play_refill)
@@ -248,12 +252,81 @@ class BatchedSelfPlayEngine:
         n = int(n)
         if n == self._run_cfg.num_simulations:
             return
+        if self._budgets is not None and n < int(self._budgets.max()):
+            raise ValueError("set_simulations: %d is below the largest per-game budget (%d); change or clear "
+                             "set_budgets first" % (n, int(self._budgets.max())))
         check(self.lib.gmz_engine_set_simulations(self.handle, n))
         if n not in self._sims_tables:
             ec = _lib.EngineCfg.from_buffer_copy(self.ecfg)
             ec.num_simulations = n
             self._sims_tables[n] = (ec, slot_need_table(ec, self.A, self.mode, self.lib))
         self._run_cfg, self._slot_need = self._sims_tables[n]
+
+    def set_budgets(self, sims=None, stream=None):
+        """A simulation budget per game from the next search on: ``sims`` an integer array [G] with
+        1 <= sims[g] <= the current simulations (NUM_SIMULATIONS, or set_simulations'), or None for the engine's
+        budget in every game again.  Game g is then searched exactly as by an engine built with sims[g]
+        simulations, in the same launches as the others; a game that has used its budget leaves the remaining
+        waves (gmz_engine_set_budgets).  The array goes up through a pinned staging pair on ``stream`` (default:
+        the current one), with no host wait.  Between moves only; not with play_refill (the arena)."""
+        s = self._stream(stream)
+        if sims is None:
+            if self._budgets is not None:
+                check(self.lib.gmz_engine_set_budgets(self.handle, None, 0, s))
+                self._budgets = None
+            return
+        if self._refill is not None:
+            raise ValueError("set_budgets: not on an engine that play_refill drives (the arena's slots change games)")
+        a = np.asarray(sims)
+        if a.shape != (self.G,) or a.dtype.kind not in "iu":
+            raise ValueError("set_budgets: expected an integer array of %d simulation counts" % self.G)
+        cap = self._run_cfg.num_simulations
+        if a.min() < 1 or a.max() > cap:
+            raise ValueError("set_budgets: every budget must be in [1, %d] (the engine's simulations), got %d..%d" %
+                             (cap, int(a.min()), int(a.max())))
+        a = a.astype(np.int32)
+        if self._budgets is not None and np.array_equal(a, self._budgets):
+            return  # the engine holds these already
+        if self._bud_dev is None:
+            self._bud_dev = torch.empty(self.G, dtype=torch.int32, device=self.device)
+            self._bud_host = [torch.zeros(self.G, dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._bud_events = [None, None]
+        i = self._bud_flip
+        self._bud_flip ^= 1
+        if self._bud_events[i] is not None:
+            self._bud_events[i].synchronize()  # (an upload two calls ago: long done)
+        self._bud_host[i].numpy()[:] = a
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            self._bud_dev.copy_(self._bud_host[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._bud_events[i] = ev
+        check(self.lib.gmz_engine_set_budgets(self.handle, ptr(self._bud_dev), _lib.nbytes(self._bud_dev), s))
+        self._budgets = a
+
+    @property
+    def budgets(self):
+        """The budgets set_budgets holds (int32 [G], a copy), None when none are set."""
+        return None if self._budgets is None else self._budgets.copy()
+
+    def _budget_waves(self, nl):
+        """(waves of the slowest game, waves per game) of searches at the legal counts ``nl`` with each game's own
+        budget (gmz_engine_waves_for_budgets)."""
+        nl = np.ascontiguousarray(nl, dtype=np.int32)
+        per = np.empty(self.G, np.int32)
+        out = ctypes.c_int32()
+        check(self.lib.gmz_engine_waves_for_budgets(
+            ctypes.byref(self._run_cfg), nl.ctypes.data_as(ctypes.c_void_p),
+            self._budgets.ctypes.data_as(ctypes.c_void_p), self.G, ctypes.byref(out),
+            per.ctypes.data_as(ctypes.c_void_p)))
+        return out.value, per
+
+    def _budget_need(self, nl):
+        """Hidden-state slots per game at the legal counts ``nl`` with budgets set: a game's own waves + 2 for
+        MuZero, its own budget + 2 for AlphaZero (slot_need_table's rule per game)."""
+        if self.mode == 0:
+            return self._budgets.astype(np.int64) + 2
+        return self._budget_waves(nl)[1].astype(np.int64) + 2
 
     def _legal_counts(self):
         """The legal-move count each game's coming search sees: 0 for a game outside the active mask."""
@@ -274,8 +347,16 @@ class BatchedSelfPlayEngine:
             self._status_event.synchronize()
             err = int(self._err_host[0])
             if err:  # a void search must not reach self-play records or the replay buffer
-                raise GmzError("engine error bits 0x%x after the last move: a search passed its game's hidden-state "
-                               "slot budget, so that game's search result is void (gmz_engine_errors)" % err)
+                what = []
+                if err & 1 or not err & 2:
+                    what.append("a search passed its game's hidden-state "
+                                "slot budget, so that game's search result is void")
+                if err & 2:
+                    what.append("a game's simulation budget was outside [1, the engine's simulations] and was clamped "
+                                "into it, so that game was not searched with the budget asked for "
+                                "(gmz_engine_set_budgets)")
+                raise GmzError("engine error bits 0x%x after the last move: %s (gmz_engine_errors)" %
+                               (err, "; ".join(what)))
             if self._refill_pending:  # play_refill: the slots' legal counts come back exact (0 = idle slot)
                 r = self._refill
                 self._n_legal[:] = r["host"].numpy()[:self.G]
@@ -302,10 +383,17 @@ class BatchedSelfPlayEngine:
         need of the two is taken.  The bases change only when a game's need does (late-game positions with
         fewer than NUM_TOP_ACTIONS legal moves); then they are copied to the device on the search's stream."""
         nl = self._legal_counts()
-        need = self._slot_need[np.clip(nl, 0, self.A)]
-        if self._status_event is not None:  # a move was played since nl was read (play_refill: or a slot was
+        if self._budgets is not None:  # each game at its own budget for the coming search, the same rule
+            if self._status_event is not None:
+                need = np.maximum(self._budget_need(np.clip(self._n_legal - 1, 0, self.A)),
+                                  self._budget_need(np.full(self.G, self.A, np.int32)))
+            else:
+                need = self._budget_need(np.clip(nl, 0, self.A))
+        elif self._status_event is not None:  # a move was played since nl was read (play_refill: or a slot was
             # refilled from an opening with >= NUM_TOP_ACTIONS legal cells, whose need is that of the empty board)
             need = np.maximum(self._slot_need[np.clip(self._n_legal - 1, 0, self.A)], self._slot_need[self.A])
+        else:
+            need = self._slot_need[np.clip(nl, 0, self.A)]
         base = np.zeros(self.G, np.int64)
         np.cumsum(need[:-1], out=base[1:])
         total = int(base[-1] + need[-1])
@@ -341,12 +429,16 @@ class BatchedSelfPlayEngine:
     def errors(self, reset=False):
         """Sticky error bits of the engine's kernels (synchronises the device; gmz_engine_errors): bit 0 = a
         search created more nodes than its game's hidden-state budget (its result is void; no other game's
-        states were touched)."""
+        states were touched); bit 1 = a simulation budget handed to gmz_engine_set_budgets was outside [1, the
+        engine's simulations] and was clamped into that range (that game searched with 1 or with the engine's
+        budget; every other game is untouched)."""
         out = ctypes.c_int32()
         check(self.lib.gmz_engine_errors(self.handle, ctypes.byref(out), 1 if reset else 0))
         return out.value
 
     def waves_needed(self):
+        if self._budgets is not None:  # the slowest game at its own budget
+            return self._budget_waves(self._legal_counts())[0]
         out = ctypes.c_int32()
         nl = np.ascontiguousarray(self._legal_counts(), dtype=np.int32)
         check(self.lib.gmz_engine_waves_for_legal(ctypes.byref(self._run_cfg), nl.ctypes.data_as(ctypes.c_void_p),
@@ -427,6 +519,9 @@ class BatchedSelfPlayEngine:
         G, dev = self.G, self.device
         if match.A != self.A:
             raise ValueError("play_refill: the book's boards are not this engine's size")
+        if self._budgets is not None:
+            raise ValueError("play_refill: not with per-game budgets (set_budgets); a refilled slot starts another "
+                             "game, whose budget nobody set")
         r = self._refill
         if r is None:
             i32 = torch.int32
@@ -606,6 +701,24 @@ class SplitSelfPlayEngine:
     def set_active(self, mask=None):
         for i, e in enumerate(self.engines):
             e.set_active(None if mask is None else np.asarray(mask).reshape(self.G)[i * self.g:(i + 1) * self.g])
+
+    def set_budgets(self, sims=None):
+        """BatchedSelfPlayEngine.set_budgets, each part its own rows; uploaded on the caller's stream, which the
+        parts' streams join at the next search."""
+        if sims is not None:
+            sims = np.asarray(sims)
+            if sims.shape != (self.G,):
+                raise ValueError("set_budgets: expected an integer array of %d simulation counts" % self.G)
+            cap = self.engines[0]._run_cfg.num_simulations
+            if sims.dtype.kind not in "iu" or sims.min() < 1 or sims.max() > cap:  # before any part uploads
+                raise ValueError("set_budgets: every budget must be an integer in [1, %d]" % cap)
+        for i, e in enumerate(self.engines):
+            e.set_budgets(None if sims is None else sims[i * self.g:(i + 1) * self.g])
+
+    @property
+    def budgets(self):
+        parts = [e._budgets for e in self.engines]
+        return None if parts[0] is None else np.concatenate(parts)
 
     def reset_games(self, mask=None):
         for i, e in enumerate(self.engines):

@@ -49,10 +49,14 @@ from .replay import ReplayBuffer, slices_from_game
 from .weight_sync import broadcast_state_dict
 
 
+BUDGET_SEED = 0x5EED0B  # SelfPlay's budget draws: RandomState(seed + BUDGET_SEED), G uniforms per move
+
+
 class SelfPlay:
     """G games on this rank's GPU (the self-play half of the worker loop, worker.py)."""
 
-    def __init__(self, cfg, num_games, state_dict, seed=0, precision="fp16", streams=None, openings=None):
+    def __init__(self, cfg, num_games, state_dict, seed=0, precision="fp16", streams=None, openings=None,
+                 fast_sims=None, full_prob=1.0):
         from . import engine as E, network as N
         from .worker import GameHistory
         c = cfg
@@ -69,6 +73,16 @@ class SelfPlay:
         self.missed = (torch.zeros(self.G, dtype=torch.int32, device=dev), torch.zeros(self.G, dtype=torch.int32, device=dev))
         self.pending = None
         self.moves = 0
+        # playout-cap randomisation: with fast_sims set, each game searches a move with NUM_SIMULATIONS with
+        # probability full_prob and with fast_sims otherwise (engine.set_budgets); every position is recorded alike
+        self.fast_sims, self.full_prob = None if fast_sims is None else int(fast_sims), float(full_prob)
+        if self.fast_sims is not None:
+            if not 1 <= self.fast_sims <= c.NUM_SIMULATIONS:
+                raise ValueError("fast_sims must be in [1, NUM_SIMULATIONS = %d]" % c.NUM_SIMULATIONS)
+            if not 0.0 <= self.full_prob <= 1.0:
+                raise ValueError("full_prob must be in [0, 1]")
+        self.budget_rs = np.random.RandomState((int(seed) + BUDGET_SEED) % (2 ** 32))
+        self.budgets = None  # the last move's simulations per game (int32 [G]); None without fast_sims
         self.ingest_buffer = self.ingest_stream = None
 
     def ingest_into(self, buffer, stream=None):
@@ -90,6 +104,10 @@ class SelfPlay:
         (GameHistory.harvest tuples; after ``ingest_into`` their first five fields)."""
         e, h = self.eng, self.hist
         b, p, lm, mc = e.game_state()
+        if self.fast_sims is not None:
+            u = self.budget_rs.random_sample(self.G)
+            self.budgets = np.where(u < self.full_prob, self.cfg.NUM_SIMULATIONS, self.fast_sims).astype(np.int32)
+            e.set_budgets(self.budgets)
         pol, val, act = e.search()
         e.winning_scan(b, p, act, counters=self.missed)
         h.record(b, p, lm, mc, pol, val, act)

@@ -117,6 +117,7 @@ class _HipGumbelMCTS:
         except Empty:
             pass
         eng = self._get_engine()
+        eng.set_budgets(None)
         self._net.hidden.clear()
         A = eng.A
         board = np.asarray(game.board, dtype=np.int8).reshape(1, -1)
@@ -135,8 +136,11 @@ class _HipGumbelMCTS:
         return pol[0].cpu().numpy().astype(np.float64), np.float32(val[0].item()), a
 
 
-    def search_batch(self, games):
+    def search_batch(self, games, num_simulations=None):
         """G games in one batched search -> (policy f64[G,A], value f32[G], action int32[G]).
+        ``num_simulations``: optionally a budget per game (integers in [1, the config's NUM_SIMULATIONS]); game g
+        is then searched as by an adapter built with NUM_SIMULATIONS = num_simulations[g]
+        (BatchedSelfPlayEngine.set_budgets).
 
         Same results as ``[self.search(g) for g in games]`` from the same global RandomState (the
         Gumbel noise is drawn game after game, mcts.py:312); the network requests still go through
@@ -154,6 +158,7 @@ class _HipGumbelMCTS:
         lms = [-1 if g.last_move is None else int(g.last_move[0]) * S + int(g.last_move[1]) for g in games]
         mcs = [getattr(g, "move_count", int((b != 0).sum())) for g, b in zip(games, boards)]
         eng.set_positions(boards, [g.current_player for g in games], lms, mcs)
+        eng.set_budgets(None if num_simulations is None else np.asarray(num_simulations).reshape(-1))
         gumbel = np.random.gumbel(0, 1, (G, A))
         try:
             pol, val, act = eng.search(gumbel=gumbel)

@@ -128,7 +128,8 @@ int gmz_engine_set_hidden_bases(gmz_engine *e, const int32_t *hbase_dev, void *s
  * that game's last slot instead of the next game's.  (ABI 8) */
 int gmz_engine_set_hidden_budget(gmz_engine *e, const int32_t *budget_dev, void *stream);
 /* Sticky error bits of the engine's kernels into *out (synchronises the device); reset != 0 clears them.
- * Bit 0: a hidden-state slot past a game's budget (gmz_engine_set_hidden_budget).  (ABI 8) */
+ * Bit 0: a hidden-state slot past a game's budget (gmz_engine_set_hidden_budget).  (ABI 8)
+ * Bit 1: a simulation budget outside [1, num_simulations], clamped (gmz_engine_set_budgets). */
 int gmz_engine_errors(gmz_engine *e, int32_t *out, int reset);
 /* The same error word copied stream-ordered (no synchronisation) to dst (host-pinned or device int32): the engine
  * checks it once per move, where it already waits for the previous move's status (engine.py).  (ABI 10) */
@@ -205,6 +206,21 @@ int gmz_engine_set_active(gmz_engine *e, const uint8_t *mask_dev, void *stream);
  * engine created with this budget (an arena gives each network its own).  Call it between moves; the caller's
  * gmz_engine_waves_for_legal must use the same number.  Host state only: nothing is launched. */
 int gmz_engine_set_simulations(gmz_engine *e, int num_simulations);
+/* A simulation budget per game (additive, ABI stays 10): budget_dev int32[G] is copied (stream-ordered) into the
+ * engine and holds from the next gmz_engine_begin_move on; game g then searches exactly as an engine created with
+ * num_simulations = budget_dev[g] would, in the same launches as its neighbours (a game that has used its budget
+ * joins no further wave: in_slot = out_slot = -1).  The current num_simulations (creation, or
+ * gmz_engine_set_simulations) stays the upper bound and the budget of every game while none is set: a value outside
+ * [1, num_simulations] is clamped into that range by gmz_engine_begin_move and sets error bit 1
+ * (gmz_engine_errors).  NULL (with budget_bytes 0) clears the budgets.  budget_bytes must be 4 * G; a null engine
+ * or another byte count is refused before any device work.  Call it between moves. */
+int gmz_engine_set_budgets(gmz_engine *e, const int32_t *budget_dev, size_t budget_bytes, void *stream);
+/* gmz_engine_waves_for_legal with game g's own budget: budget_host int32[G] (NULL = cfg->num_simulations for every
+ * game; a value outside [1, cfg->num_simulations] is refused) -> *out_max = the waves of the slowest game and, if
+ * out_per_game is not NULL, out_per_game int32[G] = each game's own waves (its hidden-state slots are that + 2).
+ * Host only; both functions share one replay of the schedule. */
+int gmz_engine_waves_for_budgets(const gmz_engine_cfg *cfg, const int32_t *n_legal_host, const int32_t *budget_host,
+                                 int G, int32_t *out_max, int32_t *out_per_game);
 /* gmz_engine_play (no reset) plus the match bookkeeping of an arena, in one launch.  The engine's G slots play the
  * 2 * n_openings games of a match between network 0 and network 1: game id = 2 * opening + first mover.
  * Per slot g:

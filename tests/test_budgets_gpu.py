@@ -1,0 +1,376 @@
+"""A simulation budget per game, mixed in one search batch (gmz_engine_set_budgets, engine.set_budgets,
+loop.SelfPlay(fast_sims=...), search_batch(num_simulations=...)) on the GPU.
+
+Game g with budget n must be the search of an engine built with NUM_SIMULATIONS = n: every comparison is with the C
+oracle run at that game's budget on the same position and noise, at the bounds of tests/test_engine_gpu.py: action,
+root value, root child visits, root N/W and MinMaxStats max/min exactly, improved policy within 1e-12 (1e-6 at 6x6,
+the reference's float32 softmax path).  A full board has no search: its policy, value and action (-1) are compared,
+its root statistics are not (the oracle returns before it makes a root)."""
+import types
+
+import numpy as np
+import pytest
+
+import oracle
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+POLICY_ATOL = 1e-12
+POLICY_ATOL_F32 = 1e-6
+
+
+@pytest.fixture(scope="module")
+def gmz():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import datou_gomoku_muzero_amd.engine as E
+    import datou_gomoku_muzero_amd._lib as L
+    L.load()
+    return E
+
+
+def _engine(E, size, sims, mode, G, split=False, **kw):
+    cls = E.SplitSelfPlayEngine if split else E.BatchedSelfPlayEngine
+    return cls(None, num_games=G, BOARD_SIZE=size, NUM_SIMULATIONS=sims, MCTS_IMPLEMENTATION=mode, **kw)
+
+
+def _run(eng, boards, players, lastm, gumbel):
+    eng.set_positions(boards, players, lastm)
+    pol, val, act = eng.search(gumbel=gumbel)
+    visits, rn, rw, mx, mn = eng.root_stats()
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in (pol, val, act, visits, rn, rw, mx, mn))
+
+
+def _errors(eng):
+    return [e.errors() for e in getattr(eng, "engines", [eng])]
+
+
+def _positions(size, G, rs):
+    """G positions of alternating colours: game 0 a full board, game 1 one empty cell, games 2 and 3 with 5 and 15
+    empty cells (fewer than NUM_TOP_ACTIONS = 16), the rest random from the empty board to one empty cell."""
+    A = size * size
+    stones = [A, A - 1, A - 5, A - 15] + [int(rs.randint(0, A)) for _ in range(G - 4)]
+    boards = np.zeros((G, A), np.int8)
+    players = np.ones(G, np.int8)
+    lastm = np.full(G, -1, np.int32)
+    for g, n in enumerate(stones[:G]):
+        cells = rs.permutation(A)[:n]
+        boards[g, cells[0::2]] = 1
+        boards[g, cells[1::2]] = -1
+        players[g] = 1 if n % 2 == 0 else -1
+        lastm[g] = cells[-1] if n else -1
+    return boards, players, lastm
+
+
+def _oracle(size, mode, boards, players, lastm, gumbel, budgets):
+    out = []
+    for g in range(len(budgets)):
+        cfg = oracle.make_cfg(size, int(budgets[g]), mode)
+        out.append(oracle.search(cfg, boards[g], players[g], None if lastm[g] < 0 else lastm[g],
+                                 int(np.count_nonzero(boards[g])), gumbel[g]))
+    return out
+
+
+def _diverging(size, got, want, boards):
+    pol, val, act, visits, rn, rw, mx, mn = got
+    tol = POLICY_ATOL_F32 if size <= 6 else POLICY_ATOL
+    bad = []
+    for g, (opol, oval, oact, orv, st) in enumerate(want):
+        ok = act[g] == oact and val[g] == oval and np.abs(pol[g] - opol).max() <= tol
+        if (boards[g] == 0).any():  # a searched game: the root statistics too
+            ok = ok and ((visits[g] == orv).all() and rn[g] == st["root_n"] and rw[g] == st["root_w"]
+                         and mx[g] == st["mm_max"] and mn[g] == st["mm_min"])
+        else:
+            ok = ok and act[g] == -1
+        if not ok:
+            bad.append(g)
+    return bad
+
+
+# the mixed-budget cases: (size, cap, mode, G, budgets); 0 in a list = drawn below
+CASES = {
+    "mz9": (9, 50, "MuZero", 16, [50, 1, 16, 17, 33, 2, 49, 50, 15, 31, 32, 7, 1, 50, 25, 40]),
+    "mz15": (15, 400, "MuZero", 12, [400, 16, 1, 17, 33, 400, 32, 399, 100, 1, 50, 200]),
+    "az9": (9, 50, "AlphaZero", 8, [50, 1, 2, 17, 33, 50, 16, 9]),
+    "mz6": (6, 400, "MuZero", 8, [400, 1, 36, 37, 100, 17, 399, 64]),
+}
+_CASE_DATA = {}
+
+
+def _case(name):
+    """Positions, noise and the oracle's per-game results of a case, computed once."""
+    if name not in _CASE_DATA:
+        size, cap, mode, G, budgets = CASES[name]
+        rs = np.random.RandomState(size * 1000 + cap)
+        boards, players, lastm = _positions(size, G, rs)
+        gumbel = rs.gumbel(0, 1, (G, size * size))
+        budgets = np.array(budgets, np.int32)
+        assert budgets.shape == (G,) and budgets.min() >= 1 and budgets.max() == cap
+        # the cases the positions must hold: a full board, one legal move, fewer than 16
+        legal = (boards == 0).sum(1)
+        assert legal[0] == 0 and legal[1] == 1 and ((legal > 1) & (legal < 16)).any() and (legal >= 16).any()
+        want = _oracle(size, mode, boards, players, lastm, gumbel, budgets)
+        _CASE_DATA[name] = (boards, players, lastm, gumbel, budgets, want)
+    return _CASE_DATA[name]
+
+
+@pytest.mark.parametrize("name,kw", [
+    ("mz9", {}), ("mz15", {}), ("az9", {}), ("mz6", {}),
+    ("mz15", dict(descent_hint=False)), ("mz15", dict(layout="lists")), ("mz15", dict(split=True, parts=2)),
+    ("mz15", dict(pair=True)),
+], ids=["mz9", "mz15", "az9", "mz6", "mz15-nohint", "mz15-lists", "mz15-split", "mz15-pair"])
+def test_mixed_budgets_match_the_oracle_at_each_games_budget(gmz, name, kw):
+    size, cap, mode, G, _ = CASES[name]
+    boards, players, lastm, gumbel, budgets, want = _case(name)
+    eng = _engine(gmz, size, cap, mode, G, **kw)
+    eng.set_budgets(budgets)
+    assert np.array_equal(eng.budgets, budgets)
+    got = _run(eng, boards, players, lastm, gumbel)
+    bad = _diverging(size, got, want, boards)
+    assert not bad, "games diverging from the oracle at their budget: %s (budgets %s)" % (bad, budgets[bad])
+    assert _errors(eng) == [0] * len(_errors(eng))
+    # the move ran the waves of its slowest game, and each game got the slots of its own search
+    for e in getattr(eng, "engines", [eng]):
+        mx, per = e._budget_waves(e._legal_counts())
+        assert e.waves_last == mx == per.max()
+        if mode == "MuZero":
+            assert np.array_equal(e.hidden_budget.cpu().numpy(), per + 2)
+        else:
+            assert np.array_equal(e.hidden_budget.cpu().numpy(), e._budgets + 2)
+    eng.close()
+
+
+def test_uniform_and_cleared_budgets_equal_an_engine_without_budgets(gmz):
+    size, cap, mode, G, _ = CASES["mz9"]
+    boards, players, lastm, gumbel, budgets, _ = _case("mz9")
+    plain = _engine(gmz, size, cap, mode, G)
+    want = _run(plain, boards, players, lastm, gumbel)
+    eng = _engine(gmz, size, cap, mode, G)
+    eng.set_budgets(np.full(G, cap, np.int64))
+    uniform = _run(eng, boards, players, lastm, gumbel)
+    eng.set_budgets(budgets)
+    mixed = _run(eng, boards, players, lastm, gumbel)
+    eng.set_budgets(None)
+    assert eng.budgets is None
+    cleared = _run(eng, boards, players, lastm, gumbel)
+    for a, b, c in zip(want, uniform, cleared):
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+    assert not np.array_equal(mixed[3], want[3])  # (the mixed move did search with other budgets)
+    assert eng.errors() == 0 and plain.errors() == 0
+
+
+def test_late_game_slots_follow_each_games_budget(gmz):
+    """Six moves of search + play from near-full 9x9 boards (3..24 legal moves, games ending and restarting from the
+    empty board) with fixed mixed budgets: the hidden-state slots are placed one ply behind from each game's own
+    budget; every action equals the oracle's at that budget and no search passes its slots."""
+    size, cap, G, moves = 9, 50, 16, 6
+    A = size * size
+    rs = np.random.RandomState(31)
+    boards = np.zeros((G, A), np.int8)
+    players = np.ones(G, np.int8)
+    lastm = np.full(G, -1, np.int32)
+    for g in range(G):  # 57..78 stones, alternating colours
+        n = 57 + (g * 7) % 22
+        cells = rs.permutation(A)[:n]
+        boards[g, cells[0::2]] = 1
+        boards[g, cells[1::2]] = -1
+        players[g] = 1 if n % 2 == 0 else -1
+        lastm[g] = cells[-1]
+    budgets = np.array([50, 1, 8, 17, 33, 50, 2, 16, 49, 50, 5, 24, 50, 12, 40, 3], np.int32)
+    eng = _engine(gmz, size, cap, "MuZero", G)
+    eng.set_positions(boards, players, lastm)
+    eng.set_budgets(budgets)
+    used = []
+    for mv in range(moves):
+        gumbel = rs.gumbel(0, 1, (G, A))
+        _, _, act = eng.search(gumbel=gumbel)
+        used.append(eng.hidden_slots_used)
+        act = act.cpu().numpy().copy()
+        status = eng.play(reset_finished=True).cpu().numpy()
+        assert eng.net.pool.numel() >= eng.hidden_slots_used
+        want = _oracle(size, "MuZero", boards, players, lastm, gumbel, budgets)
+        for g in range(G):
+            oact = want[g][2]
+            assert act[g] == oact, (mv, g, int(budgets[g]))
+            boards[g, oact] = players[g]
+            lastm[g] = oact
+            players[g] = -players[g]
+            e = oracle.game_ended(boards[g], size, oact, int(np.count_nonzero(boards[g])))
+            assert status[g] == (2 if e is None else e)
+            if e is not None:
+                boards[g] = 0
+                players[g] = 1
+                lastm[g] = -1
+    assert len(set(used)) > 1, used  # the placement moved with the legal counts
+    assert eng.errors() == 0
+
+
+def test_bad_budgets_through_the_raw_entry_point_are_clamped_and_flagged(gmz):
+    """gmz_engine_set_budgets with 0 and cap + 1 in the device array (engine.set_budgets refuses them on the host):
+    the two games search with 1 and cap, error bit 1 is raised, every other game searches at its own budget, and the
+    product path refuses to go on at the next move."""
+    from datou_gomoku_muzero_amd._lib import GmzError, check, ptr
+    size, cap, mode, G, _ = CASES["mz9"]
+    G = 8
+    boards, players, lastm, gumbel = (x[4:4 + G] for x in _case("mz9")[:4])
+    raw = np.array([7, 50, 0, 33, 51, 1, 16, 20], np.int32)
+    eff = np.array([7, 50, 1, 33, 50, 1, 16, 20], np.int32)
+    eng = _engine(gmz, size, cap, mode, G)
+    dev = torch.as_tensor(raw).cuda()
+    L, s = eng.lib, eng._stream()
+    assert L.gmz_engine_set_budgets(eng.handle, ptr(dev), 4 * G - 4, s) < 0  # a wrong byte count: refused
+    assert str(4 * G - 4) in L.gmz_last_error().decode() and str(4 * G) in L.gmz_last_error().decode()
+    assert L.gmz_engine_set_budgets(eng.handle, None, 4 * G, s) < 0
+    check(L.gmz_engine_set_budgets(eng.handle, ptr(dev), 4 * G, s))
+    got = _run(eng, boards, players, lastm, gumbel)
+    want = _oracle(size, mode, boards, players, lastm, gumbel, eff)
+    assert not _diverging(size, got, want, boards)
+    assert eng.errors() == 2
+    eng.play()
+    with pytest.raises(GmzError, match="simulation budget") as ei:
+        eng.search()
+    assert "hidden-state" not in str(ei.value)
+    assert eng.errors(reset=True) == 2 and eng.errors() == 0
+    check(L.gmz_engine_set_budgets(eng.handle, None, 0, s))  # cleared: the engine's budget in every game again
+    got = _run(eng, boards, players, lastm, gumbel)
+    want = _oracle(size, mode, boards, players, lastm, gumbel, np.full(G, cap))
+    assert not _diverging(size, got, want, boards) and eng.errors() == 0
+
+
+def test_host_refusals(gmz):
+    size, cap, mode, G = 9, 50, "MuZero", 8
+    eng = _engine(gmz, size, cap, mode, G)
+    ok = np.full(G, 20, np.int32)
+    for bad in (0, cap + 1, -1):
+        b = ok.copy()
+        b[3] = bad
+        with pytest.raises(ValueError, match="budget"):
+            eng.set_budgets(b)
+    with pytest.raises(ValueError):
+        eng.set_budgets(ok[:-1])
+    with pytest.raises(ValueError):
+        eng.set_budgets(ok.astype(np.float32))
+    assert eng.budgets is None
+    eng.set_budgets(ok)
+    with pytest.raises(ValueError, match="largest per-game budget"):
+        eng.set_simulations(19)
+    eng.set_simulations(20)
+    with pytest.raises(ValueError, match="budget"):  # the bound is the current simulations
+        eng.set_budgets(np.full(G, 21, np.int32))
+    with pytest.raises(ValueError, match="play_refill"):
+        eng.play_refill(types.SimpleNamespace(A=eng.A), 0)
+    eng.set_budgets(None)
+    eng.set_simulations(cap)
+    sp = _engine(gmz, size, cap, mode, G, split=True, parts=2)
+    b = ok.copy()
+    b[G - 1] = cap + 1  # in the second part: nothing reaches the first either
+    with pytest.raises(ValueError, match="budget"):
+        sp.set_budgets(b)
+    assert sp.budgets is None and all(e.budgets is None for e in sp.engines)
+    sp.set_budgets(np.arange(1, G + 1))
+    assert np.array_equal(sp.budgets, np.arange(1, G + 1))
+    assert np.array_equal(sp.engines[1].budgets, np.arange(G // 2 + 1, G + 1))
+    assert eng.errors() == 0
+
+
+# ------------------------------------------------------------------------------------------ loop.SelfPlay
+SP_G, SP_MOVES, SP_SEED = 8, 12, 3
+
+
+def _selfplay(sims, **kw):
+    """SelfPlay on a real network (6x6, 2 blocks), SP_MOVES moves: per move (policy, action, budgets), the games
+    that finished, and the engine's error words."""
+    from datou_gomoku_muzero_amd import loop as LP, weights as W
+    from datou_gomoku_muzero_amd.config import GmzConfig
+    cfg = GmzConfig(BOARD_SIZE=6, NUM_SIMULATIONS=sims, NUM_RES_BLOCKS=2)
+    sd = W.synthetic_state_dict(GmzConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=2), seed=1, with_projection=False)
+    sp = LP.SelfPlay(cfg, SP_G, sd, seed=SP_SEED, **kw)
+    calls = []
+    for e in getattr(sp.eng, "engines", [sp.eng]):
+        real = e.set_budgets
+        e.set_budgets = (lambda *a, _real=real, **k: (calls.append(1), _real(*a, **k))[1])
+    moves, done = [], []
+    for _ in range(SP_MOVES):
+        done += [tuple(int(x) for x in d[:3]) for d in sp.step()]
+        torch.cuda.synchronize()
+        moves.append((sp.eng.policy.cpu().numpy().copy(), sp.eng.action.cpu().numpy().copy(),
+                      None if sp.budgets is None else sp.budgets.copy()))
+    done += [tuple(int(x) for x in d[:3]) for d in sp.flush()]
+    errs = _errors(sp.eng)
+    sp.close()
+    return moves, done, errs, len(calls)
+
+
+def _same_games(a, b):
+    return all(np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) for x, y in zip(a[0], b[0])) and a[1] == b[1]
+
+
+def test_selfplay_fast_searches_equal_a_selfplay_built_with_the_fast_budget():
+    fast = _selfplay(32, fast_sims=8, full_prob=0.0)
+    small = _selfplay(8)
+    assert _same_games(fast, small)
+    assert all((m[2] == 8).all() for m in fast[0]) and fast[2] == [0] * len(fast[2])
+    assert small[3] == 0 and all(m[2] is None for m in small[0])  # fast_sims=None: no set_budgets call at all
+
+
+def test_selfplay_full_prob_one_equals_the_plain_selfplay():
+    full = _selfplay(32, fast_sims=8, full_prob=1.0)
+    plain = _selfplay(32)
+    assert _same_games(full, plain)
+    assert all((m[2] == 32).all() for m in full[0]) and full[2] == [0] * len(full[2])
+
+
+def test_selfplay_mixed_budgets_are_the_stated_draw_and_reproducible():
+    from datou_gomoku_muzero_amd import loop as LP
+    a = _selfplay(32, fast_sims=8, full_prob=0.5)
+    b = _selfplay(32, fast_sims=8, full_prob=0.5)
+    assert _same_games(a, b) and a[2] == [0] * len(a[2])
+    rs = np.random.RandomState(SP_SEED + LP.BUDGET_SEED)
+    for pol, act, bud in a[0]:
+        want = np.where(rs.random_sample(SP_G) < 0.5, 32, 8)
+        assert np.array_equal(bud, want)
+        assert (act >= 0).all() and np.allclose(pol.sum(1), 1.0, atol=1e-9)  # every game searched and recorded
+    buds = np.stack([m[2] for m in a[0]])
+    assert (buds == 8).any() and (buds == 32).any()
+    assert a[3] == SP_MOVES * len(a[2])  # one set_budgets call per move and engine
+
+
+# ------------------------------------------------------------------------------------------ adapters
+@pytest.mark.parametrize("fname", ["mcts_mz9_50.npz", "mcts_az9_50.npz"])
+def test_search_batch_with_budgets_equals_adapters_built_with_them(golden, fname):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from queue_helpers import Game, ServerQueue
+    from datou_gomoku_muzero_amd import mcts
+    from datou_gomoku_muzero_amd.config import GmzConfig
+    d = golden(fname)
+    size, mode, sims = int(d["size"]), str(d["mode"]), int(d["sims"])
+    games = []
+    for i in range(len(d["action"])):
+        lm = int(d["lastmove"][i])
+        games.append(Game(d["board"][i].reshape(size, size), d["player"][i], None if lm < 0 else (lm // size, lm % size)))
+    budgets = [(sims, 1, 16, 17, 33, 7, 2, sims - 1)[i % 8] for i in range(len(games))]
+    adapters = {}
+    np.random.seed(int(d["seed"]))
+    seq = []
+    for g, b in zip(games, budgets):  # one adapter per budget, the noise drawn game after game
+        if b not in adapters:
+            q = ServerQueue(size * size)
+            adapters[b] = mcts.make_engine(0, q, q, cfg=GmzConfig(BOARD_SIZE=size, NUM_SIMULATIONS=b,
+                                                                  MCTS_IMPLEMENTATION=mode))
+        seq.append(adapters[b].search(g))
+    q2 = ServerQueue(size * size)
+    e2 = mcts.make_engine(0, q2, q2, cfg=GmzConfig(BOARD_SIZE=size, NUM_SIMULATIONS=sims, MCTS_IMPLEMENTATION=mode))
+    np.random.seed(int(d["seed"]))
+    pol, val, act = e2.search_batch(games, num_simulations=budgets)
+    for i, (p, v, a) in enumerate(seq):
+        assert act[i] == a and val[i] == v, (i, budgets[i])
+        assert np.abs(pol[i] - p).max() <= 1e-12
+    # without budgets the same adapter searches every game at the config's simulations again
+    np.random.seed(int(d["seed"]))
+    pol, val, act = e2.search_batch(games)
+    assert act.tolist() == d["action"].tolist()
+    with pytest.raises(ValueError, match="budget"):
+        e2.search_batch(games, num_simulations=[sims + 1] * len(games))
