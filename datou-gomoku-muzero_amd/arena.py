@@ -13,8 +13,14 @@ idle slots) and the keyed Gumbel noise (gmz_gumbel_keyed).  DESIGN.md §8b has t
   * noise: keyed by (seed, opening index, ply of the game) — not by the slot, not by who moves first;
   * the host's legal-count mirror comes back exact with each status, one ply behind.
 
+Either side may be an AnchorPlayer instead of a network: a fixed opponent that does not search ("threat": complete a
+five, block one, otherwise build or break lines; "uniform": a random legal move), whose move is one launch
+(gmz_game_anchor_move) on the engine's boards.  Anchors stay the same from run to run, so a score against one is an
+absolute strength reading.
+
     python -m datou_gomoku_muzero_amd.arena --a CKPT --b CKPT --games N [--precision-a fp16 --precision-b bf16
                                                                          --sims-a 400 --sims-b 200]
+    python -m datou_gomoku_muzero_amd.arena --a CKPT --b anchor:threat --games N [--anchor-scale X]
 """
 import argparse
 import json
@@ -173,6 +179,40 @@ def summarise(winner_colour, length, book_players, moves=None):
                        pair_scores=[float(x) for x in pairs])
 
 
+# ---------------------------------------------------------------------------------------------- anchors
+ANCHOR_PREFIX = "anchor:"
+
+
+@dataclass
+class AnchorPlayer:
+    """A fixed opponent that does not search (engine.anchor_move), as a side of an Arena.  ``kind``
+    "threat": the one-ply threat player; "uniform": a random legal move.  ``scale`` multiplies the keyed Gumbel noise
+    added to the cell scores (None: 0 for threat, where the noise only breaks ties, and 1 for uniform)."""
+    kind: str = "threat"
+    scale: float = None
+
+    def checked(self):
+        """(kind, scale) with the default scale filled in; ValueError for an unknown kind or a scale that is
+        negative or not finite."""
+        if self.kind not in ("threat", "uniform"):
+            raise ValueError("AnchorPlayer: kind must be 'threat' or 'uniform', got %r" % (self.kind,))
+        scale = (0.0 if self.kind == "threat" else 1.0) if self.scale is None else float(self.scale)
+        if not (scale >= 0.0 and math.isfinite(scale)):
+            raise ValueError("AnchorPlayer: scale must be finite and >= 0, got %r" % (self.scale,))
+        return self.kind, scale
+
+    @property
+    def name(self):
+        return ANCHOR_PREFIX + self.kind
+
+
+def anchor_from_name(name, scale=None):
+    """AnchorPlayer of "anchor:threat" / "anchor:uniform"; None for any other string (a checkpoint path)."""
+    if isinstance(name, str) and name.startswith(ANCHOR_PREFIX):
+        return AnchorPlayer(name[len(ANCHOR_PREFIX):], scale)
+    return None
+
+
 # ---------------------------------------------------------------------------------------------- arena
 def default_arena_streams(cfg, num_slots):
     """Engines (HIP streams) of an arena, as measured (profiles/arena.txt): two half-size engines offset by one ply
@@ -183,25 +223,31 @@ def default_arena_streams(cfg, num_slots):
 
 
 class Arena:
-    """A match between two engine backends (network.GomokuNetHip of any precision or depth, or
-    engine.HashNetBackend) on ``num_slots`` slots.  ``openings``: (boards, players, last_moves, move_counts) as
-    paired_openings returns; every opening is played twice, once with each network moving first.  ``streams=2``:
-    two engines of num_slots / 2 slots on two HIP streams, offset by one ply so that both networks work at every
-    ply; the games are the same ones.  ``sims=(n_a, n_b)``: a simulation budget per network."""
+    """A match between two sides, each an engine backend (network.GomokuNetHip of any precision or depth, or
+    engine.HashNetBackend) or an AnchorPlayer, on ``num_slots`` slots.  ``openings``: (boards, players, last_moves,
+    move_counts) as paired_openings returns; every opening is played twice, once with each side moving first.
+    ``streams=2``: two engines of num_slots / 2 slots on two HIP streams, offset by one ply so that both sides work
+    at every ply; the games are the same ones.  ``sims=(n_a, n_b)``: a simulation budget per network (ignored for
+    an anchor side).  On an anchor's ply an engine runs the keyed noise, the anchor's launch and play_refill, and
+    no search."""
 
     def __init__(self, cfg, net_a, net_b, num_slots, openings, seed=0, record_moves=False, streams=None,
                  device="cuda", sims=None, **overrides):
         from . import engine as E
         from .config import from_any
         self.cfg = from_any(cfg, **overrides)
+        # per side: None for a network, (kind, scale) for an anchor
+        self.anchors = [s.checked() if isinstance(s, AnchorPlayer) else None for s in (net_a, net_b)]
         self.book = check_book(openings, self.cfg)
         # simulations per search of network A and of network B (default: the configuration's for both); the
         # engines are built for the larger budget
         self.sims = (self.cfg.NUM_SIMULATIONS,) * 2 if sims is None else (int(sims[0]), int(sims[1]))
-        if min(self.sims) < 1:
+        searching = [n for n, a in zip(self.sims, self.anchors) if a is None]  # an anchor does not search
+        if searching and min(searching) < 1:
             raise ValueError("Arena: sims must be positive")
-        if max(self.sims) != self.cfg.NUM_SIMULATIONS:
-            self.cfg = from_any(self.cfg, NUM_SIMULATIONS=max(self.sims))
+        built = max(searching) if searching else 1  # anchors only: the engines keep the boards, their trees idle
+        if built != self.cfg.NUM_SIMULATIONS:
+            self.cfg = from_any(self.cfg, NUM_SIMULATIONS=built)
         self.n_openings = self.book[0].shape[0]
         if streams is None:
             streams = default_arena_streams(self.cfg, num_slots)
@@ -215,20 +261,40 @@ class Arena:
         self.seed, self.record_moves, self.parts = int(seed), bool(record_moves), int(streams)
         self.num_slots = int(num_slots)
         g = self.num_slots // self.parts
-        if self.parts > 1:  # a view of each network per engine: its own pool slice and workspace
-            cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-            cap = max(cus // 2, cus - E.TOWER_FREE_CUS)
-            va, vb = net_a.split(self.parts, cap), net_b.split(self.parts, cap)
-            self.nets = [(va[i], vb[i]) for i in range(self.parts)]
-            self.streams = E.engine_streams(self.device, self.parts)
-        else:
-            self.nets = [(net_a, net_b)]
-            self.streams = [None]
-        self.engines = [E.BatchedSelfPlayEngine(self.cfg, g, self.nets[i][i % 2], device, self.seed)
-                        for i in range(self.parts)]
+        self.streams = E.engine_streams(self.device, self.parts) if self.parts > 1 else [None]
+        self.nets = self._views(net_a, net_b)
+        # an engine starts with its first mover's backend, or the other side's when that one is an anchor (anchors
+        # only: None, the engine's own HashNetBackend, never run)
+        first = [self.nets[i][i % 2] if self.nets[i][i % 2] is not None else self.nets[i][1 - i % 2]
+                 for i in range(self.parts)]
+        self.engines = [E.BatchedSelfPlayEngine(self.cfg, g, first[i], device, self.seed) for i in range(self.parts)]
         self.A = self.cfg.ACTION_SPACE_SIZE
         self.gumbel = [torch.zeros(g, self.A, dtype=torch.float64, device=self.device) for _ in range(self.parts)]
         self.match = None
+
+    def _views(self, net_a, net_b):
+        """Per engine the pair (A's backend, B's backend), None in an anchor's place: with two engines a view of
+        each network per engine, with its own pool slice and workspace."""
+        from . import engine as E
+        if self.parts == 1:
+            return [tuple(None if a is not None else n for n, a in zip((net_a, net_b), self.anchors))]
+        cus = self.torch.cuda.get_device_properties(self.device).multi_processor_count
+        cap = max(cus // 2, cus - E.TOWER_FREE_CUS)
+        va, vb = [[None] * self.parts if a is not None else n.split(self.parts, cap)
+                  for n, a in zip((net_a, net_b), self.anchors)]
+        return [(va[i], vb[i]) for i in range(self.parts)]
+
+    def set_sides(self, side_a, side_b, sims=None):
+        """Other sides (backends or AnchorPlayers) for the next run() on the same engines, streams and book.  A
+        network side's simulations (``sims``, default: kept) must be within what the engines were built for."""
+        anchors = [s.checked() if isinstance(s, AnchorPlayer) else None for s in (side_a, side_b)]
+        sims = self.sims if sims is None else (int(sims[0]), int(sims[1]))
+        searching = [n for n, a in zip(sims, anchors) if a is None]
+        if searching and not 1 <= min(searching) <= max(searching) <= self.cfg.NUM_SIMULATIONS:
+            raise ValueError("Arena.set_sides: sims must be in [1, %d], what the engines were built for" %
+                             self.cfg.NUM_SIMULATIONS)
+        self.anchors, self.sims = anchors, sims
+        self.nets = self._views(side_a, side_b)
 
     def close(self):
         for e in self.engines:
@@ -260,16 +326,21 @@ class Arena:
 
     def step(self):
         """One ply of every engine: engine i searches with network (ply + i) % 2 under the keyed noise, plays, and
-        refills its idle slots with openings of the other network, which moves next."""
-        gens = []
+        refills its idle slots with openings of the other network, which moves next.  Where that side is an anchor
+        the search is one launch of its move rule on the same noise."""
+        gens, actions = [], [None] * self.parts
         for i, e in enumerate(self.engines):
             k = (self.ply + i) % 2
-            e.net = self.nets[i][k]
-            e.set_simulations(self.sims[k])
             with self._ctx(i):
                 e.keyed_gumbel(self.gumbel[i], self.streams[i])
-                gens.append(e.search_steps(self.gumbel[i], self.streams[i]))
-        live = list(enumerate(gens))
+                if self.anchors[k] is not None:
+                    kind, scale = self.anchors[k]
+                    actions[i] = e.anchor_move(self.gumbel[i], kind, scale, self.streams[i])
+                    continue
+                e.net = self.nets[i][k]
+                e.set_simulations(self.sims[k])
+                gens.append((i, e.search_steps(self.gumbel[i], self.streams[i])))
+        live = list(gens)
         while live:  # one wave of each engine in turn (as SplitSelfPlayEngine.search)
             for item in list(live):
                 i, gen = item
@@ -279,8 +350,12 @@ class Arena:
                     except StopIteration:
                         live.remove(item)
         for i, e in enumerate(self.engines):
+            if actions[i] is not None:
+                # no search has read the last ply's status (a search does, to size its waves): read it before this
+                # ply's play_refill overwrites the pinned buffers, or the counters and the legal counts lose a ply
+                e._sync_status()
             with self._ctx(i):
-                e.play_refill(self.match, (self.ply + i + 1) % 2, stream=self.streams[i])
+                e.play_refill(self.match, (self.ply + i + 1) % 2, action=actions[i], stream=self.streams[i])
         self.ply += 1
 
     def finished(self):
@@ -334,20 +409,26 @@ def blocks_of(state_dict):
 
 
 def play_match(sd_a, sd_b, cfg, games, num_slots=None, precision_a="fp16", precision_b="fp16", seed=0,
-               stones=(2, 4, 6), record_moves=False, streams=None, device="cuda", sims=None):
+               stones=(2, 4, 6), record_moves=False, streams=None, device="cuda", sims=None, anchor_scale=None):
     """A match of ``games`` games (rounded up to an even number: games / 2 openings from paired_openings) between
-    the networks of two state dicts, which may differ in depth and precision.  Returns a MatchResult."""
+    the networks of two state dicts, which may differ in depth and precision.  Either side may instead be an
+    AnchorPlayer or its name ("anchor:threat", "anchor:uniform", with ``anchor_scale``).  Returns a MatchResult."""
     from . import engine as E, network as N
     from .config import from_any
+    sides = [anchor_from_name(sd, anchor_scale) or sd for sd in (sd_a, sd_b)]
     c = from_any(cfg)
     if sims is not None:
-        c = from_any(c, NUM_SIMULATIONS=max(sims))
+        searching = [n for n, sd in zip(sims, sides) if not isinstance(sd, AnchorPlayer)]
+        c = from_any(c, NUM_SIMULATIONS=max(searching) if searching else 1)
     n = max(1, (int(games) + 1) // 2)
     slots = int(num_slots) if num_slots else min(1024, 2 * n)
     if streams == 2 and slots % 2:
         slots += 1
     nets = []
-    for sd, prec in ((sd_a, precision_a), (sd_b, precision_b)):
+    for sd, prec in zip(sides, (precision_a, precision_b)):
+        if isinstance(sd, AnchorPlayer):
+            nets.append(sd)
+            continue
         cn = from_any(c, NUM_RES_BLOCKS=blocks_of(sd))
         nets.append(N.GomokuNetHip(sd, cn, num_slots=E.hidden_slots(c, slots), max_rows=slots, device=device,
                                    precision=prec))
@@ -382,8 +463,11 @@ def load_checkpoint(path):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m datou_gomoku_muzero_amd.arena", description="A match between two network checkpoints on the GPU: paired openings, "
                                              "wins / draws / losses and the Elo difference as one JSON line.")
-    ap.add_argument("--a", required=True, help="checkpoint of network A (RecordStore .db or torch.save file)")
-    ap.add_argument("--b", required=True, help="checkpoint of network B")
+    ap.add_argument("--a", required=True, help="checkpoint of network A (RecordStore .db or torch.save file), or "
+                                               "anchor:threat / anchor:uniform for a fixed opponent")
+    ap.add_argument("--b", required=True, help="checkpoint of network B, or anchor:threat / anchor:uniform")
+    ap.add_argument("--anchor-scale", type=float, default=None,
+                    help="noise scale of an anchor side (default: 0 for threat, 1 for uniform)")
     ap.add_argument("--games", type=int, required=True)
     ap.add_argument("--precision-a", default="fp16", choices=("fp16", "bf16"))
     ap.add_argument("--precision-b", default="fp16", choices=("fp16", "bf16"))
@@ -399,10 +483,13 @@ def main(argv=None):
     from .config import GmzConfig
     cfg = GmzConfig(BOARD_SIZE=a.board_size, NUM_SIMULATIONS=a.sims, MCTS_IMPLEMENTATION=a.mode)
     sims = (a.sims_a or a.sims, a.sims_b or a.sims)
-    res = play_match(load_checkpoint(a.a), load_checkpoint(a.b), cfg, a.games, a.slots or None, a.precision_a,
-                     a.precision_b, a.seed, streams=a.streams, sims=sims)
+    sides = [anchor_from_name(x, a.anchor_scale) or load_checkpoint(x) for x in (a.a, a.b)]
+    res = play_match(sides[0], sides[1], cfg, a.games, a.slots or None, a.precision_a, a.precision_b, a.seed,
+                     streams=a.streams, sims=sims)
     out = res.as_dict()
-    out.update(sims_a=sims[0], sims_b=sims[1], a=os.path.basename(a.a), b=os.path.basename(a.b), precision_a=a.precision_a, precision_b=a.precision_b)
+    names = [s.name if isinstance(s, AnchorPlayer) else os.path.basename(x) for s, x in zip(sides, (a.a, a.b))]
+    out.update(sims_a=sims[0], sims_b=sims[1], a=names[0], b=names[1], precision_a=a.precision_a,
+               precision_b=a.precision_b)
     print(json.dumps(out))
     return 0
 

@@ -160,6 +160,130 @@ GMZ_EXPORT int gmz_game_winning_scan(const int8_t *boards, const int8_t *players
   return 0;
 }
 
+namespace gmz {
+
+// One candidate of the anchor's arg-max over (key, noise, -cell), compared lexicographically; cell < 0 = none.
+struct AnchorBest {
+  double key, noise;
+  int cell;
+};
+
+__device__ __forceinline__ bool anchor_better(const AnchorBest &x, const AnchorBest &y) {
+  if (y.cell < 0) return x.cell >= 0;
+  if (x.cell < 0) return false;
+  if (x.key != y.key) return x.key > y.key;
+  if (x.noise != y.noise) return x.noise > y.noise;
+  return x.cell < y.cell;
+}
+
+// The anchor opponents' move rule: one workgroup per board (board in LDS), one thread per cell.
+// An empty cell's score sums, over the n-cell windows through it in the four directions that lie on the board
+// and hold stones of one colour only (or none), W_own[min(m, 4)] for the mover's windows and W_opp[min(m, 4)] for
+// the opponent's, m = the stones the window still lacks once the cell is taken; kind 1 scores every empty cell 0.
+// The move is the empty cell with the largest (score + scale * noise, noise, -cell); -1 on a full board and for
+// a game whose game[g] is negative.  scores (nullable) int64[G][A]: the score, -1 for an occupied cell.
+__global__ void __launch_bounds__(512) k_anchor_move(const int8_t *__restrict__ boards, const int8_t *__restrict__ players,
+                                                     const int32_t *__restrict__ game, const double *__restrict__ noise,
+                                                     int size, int n_in_row, int kind, double scale,
+                                                     int32_t *__restrict__ actions, int64_t *__restrict__ scores) {
+  __shared__ int8_t b[MAX_A];
+  __shared__ double wave_key[512 / WAVE], wave_noise[512 / WAVE];
+  __shared__ int wave_cell[512 / WAVE];
+  const int g = blockIdx.x, A = size * size;
+  if (game && game[g] < 0) {  // an idle arena slot (the whole workgroup leaves together)
+    if (threadIdx.x == 0) actions[g] = -1;
+    if (scores)
+      for (int i = threadIdx.x; i < A; i += blockDim.x) scores[(size_t)g * A + i] = -1;
+    return;
+  }
+  const int8_t *src = boards + (size_t)g * A;
+  for (int i = threadIdx.x; i < A; i += blockDim.x) b[i] = src[i];
+  __syncthreads();
+  const int p = players[g];
+  const int cell = threadIdx.x;  // blockDim.x >= A (gmz_game_anchor_move)
+  AnchorBest best = {0.0, 0.0, -1};
+  if (cell < A) {
+    int64_t sc = -1;
+    if (b[cell] == 0) {
+      sc = 0;
+      if (kind == 0) {
+        const int64_t w_own[5] = {1 << 26, 1 << 13, 1 << 6, 1 << 2, 1};
+        const int64_t w_opp[5] = {1 << 20, 1 << 10, 1 << 5, 1 << 1, 0};
+        const int r0 = cell / size, c0 = cell % size;
+        const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+        for (int d = 0; d < 4; ++d)
+          for (int o = 0; o < n_in_row; ++o) {
+            const int rs = r0 - o * dr[d], cs = c0 - o * dc[d];  // the window's first cell; its last:
+            const int re = rs + (n_in_row - 1) * dr[d], ce = cs + (n_in_row - 1) * dc[d];
+            if (rs < 0 || re >= size || cs < 0 || cs >= size || ce < 0 || ce >= size) continue;
+            int own = 0, opp = 0;
+            for (int j = 0; j < n_in_row; ++j) {
+              const int v = b[(rs + j * dr[d]) * size + cs + j * dc[d]];
+              own += v == p;
+              opp += v == -p;
+            }
+            if (opp == 0) sc += w_own[min(n_in_row - 1 - own, 4)];
+            if (own == 0) sc += w_opp[min(n_in_row - 1 - opp, 4)];
+          }
+      }
+      const double nz = noise ? noise[(size_t)g * A + cell] : 0.0;
+      best.key = (double)sc + scale * nz;
+      best.noise = nz;
+      best.cell = cell;
+    }
+    if (scores) scores[(size_t)g * A + cell] = sc;
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    AnchorBest o;
+    o.key = __shfl_xor(best.key, off);
+    o.noise = __shfl_xor(best.noise, off);
+    o.cell = __shfl_xor(best.cell, off);
+    if (anchor_better(o, best)) best = o;
+  }
+  const int wave = threadIdx.x / WAVE;
+  if (threadIdx.x % WAVE == 0) {
+    wave_key[wave] = best.key;
+    wave_noise[wave] = best.noise;
+    wave_cell[wave] = best.cell;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)blockDim.x / WAVE; ++w) {
+      const AnchorBest o = {wave_key[w], wave_noise[w], wave_cell[w]};
+      if (anchor_better(o, best)) best = o;
+    }
+    actions[g] = best.cell;
+  }
+}
+
+}  // namespace gmz
+
+GMZ_EXPORT int gmz_game_anchor_move(const int8_t *boards, const int8_t *players, const int32_t *game, const double *noise,
+                                    size_t noise_bytes, int G, int size, int n_in_row, int kind, double scale,
+                                    int32_t *actions, size_t actions_bytes, int64_t *scores, size_t scores_bytes,
+                                    void *stream) {
+  if (G <= 0 || size <= 0 || size * size > MAX_A) return fail("gmz_game_anchor_move: bad shape");
+  if (n_in_row < 1 || n_in_row > size) return fail("gmz_game_anchor_move: n_in_row must be in [1, size]");
+  if (kind != 0 && kind != 1) return fail("gmz_game_anchor_move: kind must be 0 (threat) or 1 (uniform)");
+  if (!(scale >= 0.0) || !std::isfinite(scale)) return fail("gmz_game_anchor_move: scale must be finite and >= 0");
+  if (!boards || !players || !actions) return fail("gmz_game_anchor_move: null boards, players or actions");
+  const size_t A = (size_t)size * size, cells = (size_t)G * A;
+  if (noise && noise_bytes < cells * sizeof(double))
+    return fail("gmz_game_anchor_move: noise holds " + std::to_string(noise_bytes) + " bytes, G * A * 8 = " +
+                std::to_string(cells * sizeof(double)));
+  if (actions_bytes < (size_t)G * sizeof(int32_t))
+    return fail("gmz_game_anchor_move: actions holds " + std::to_string(actions_bytes) + " bytes, G * 4 = " +
+                std::to_string((size_t)G * sizeof(int32_t)));
+  if (scores && scores_bytes < cells * sizeof(int64_t))
+    return fail("gmz_game_anchor_move: scores holds " + std::to_string(scores_bytes) + " bytes, G * A * 8 = " +
+                std::to_string(cells * sizeof(int64_t)));
+  const int threads = A <= 256 ? 256 : 512;
+  hipLaunchKernelGGL(k_anchor_move, dim3(G), dim3(threads), 0, (hipStream_t)stream, boards, players, game, noise, size,
+                     n_in_row, kind, scale, actions, scores);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
 GMZ_EXPORT int gmz_game_check_win(const int8_t *boards, int G, int size, int n_in_row, const int32_t *moves,
                                   uint8_t *out, void *stream) {
   if (G <= 0 || size <= 0 || size * size > MAX_A) return fail("gmz_game_check_win: bad shape");

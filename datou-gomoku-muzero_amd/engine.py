@@ -144,6 +144,7 @@ class BatchedSelfPlayEngine:
         self._bud_flip = 0
         self._refill = None  # play_refill's slot arrays and pinned read-back buffers (arena)
         self._refill_pending = False
+        self._state_ptrs = None  # device pointers of the engine-owned game state (anchor_move)
         self.finished_seen = 0  # the match's finished-games counter as of the last status read (play_refill)
         self.moves_played = 0   # moves counted from the statuses read after play_refill calls
         self._hb_net = None     # the backend whose pool the last placement was checked against
@@ -556,6 +557,25 @@ class BatchedSelfPlayEngine:
                                         _lib.nbytes(out), self._stream(stream)))
         return out
 
+    def anchor_move(self, noise=None, kind="threat", scale=0.0, stream=None):
+        """An anchor opponent's move (gmz_game_anchor_move, see ``anchor_move``) for the side to move on the
+        engine's own device boards, in one launch on ``stream`` with no host wait: into ``self.action``, which is
+        returned and which play_refill(action=...) takes.  ``noise``: f64[G,A] on the device (keyed_gumbel's) or
+        None.  On an engine that play_refill drives, an idle slot gets -1."""
+        if self._state_ptrs is None:
+            p = [ctypes.c_void_p() for _ in range(4)]
+            check(self.lib.gmz_engine_game_state(self.handle, *[ctypes.byref(x) for x in p]))
+            self._state_ptrs = p
+        if noise is not None and (not torch.is_tensor(noise) or noise.dtype != torch.float64
+                                  or noise.device.type != self.device.type or not noise.is_contiguous()):
+            raise ValueError("anchor_move: noise must be a contiguous float64 tensor on %s" % self.device)
+        game = self._refill["game"] if self._refill is not None else None
+        check(self.lib.gmz_game_anchor_move(
+            self._state_ptrs[0], self._state_ptrs[1], ptr(game), ptr(noise), _lib.nbytes(noise), self.G, self.size,
+            self.cfg.N_IN_ROW, anchor_kind(kind), float(scale), ptr(self.action), _lib.nbytes(self.action), None, 0,
+            self._stream(stream)))
+        return self.action
+
     def winning_scan(self, boards, players, action=None, counters=None, stream=None):
         """workers.py:49-123 find_winning_moves_rebuilt on the device for G positions (see
         ``winning_scan``); ``counters`` = (missed_fives, missed_totals) int32[G] accumulated in place."""
@@ -881,6 +901,45 @@ def winning_scan(boards, players, actions=None, n_in_row=5, counters=None, strea
     check(L.gmz_game_winning_scan(ptr(b), ptr(p), ptr(a), G, S, int(n_in_row), ptr(cls), ptr(mf), ptr(mt),
                                   _lib.stream_ptr(stream)))
     return cls
+
+
+ANCHOR_KINDS = {"threat": 0, "uniform": 1}
+
+
+def anchor_kind(kind):
+    """gmz_game_anchor_move's ``kind`` of an anchor's name: 0 for 'threat', 1 for 'uniform'."""
+    if kind not in ANCHOR_KINDS:
+        raise ValueError("anchor kind must be 'threat' or 'uniform', got %r" % (kind,))
+    return ANCHOR_KINDS[kind]
+
+
+def anchor_move(boards, players, noise=None, kind="threat", scale=0.0, n_in_row=5, game=None, scores=False,
+                stream=None):
+    """The move of a fixed non-network opponent on G boards (``gmz_game_anchor_move``; the rule: DESIGN.md §8b).
+
+    boards int8[G,S,S] and players int8[G] (the player to move) on the device; ``noise`` f64[G,S*S] or None (= 0).
+    ``kind`` 'threat' scores each empty cell by the lines it completes, blocks, builds or breaks, 'uniform' scores
+    them all 0; the move is the empty cell with the largest (score + scale * noise, noise, -cell).  With Gumbel noise
+    kind='uniform', scale=1 is a uniformly random legal move and kind='threat', scale=0 the deterministic threat
+    player whose ties the noise breaks.  ``game`` int32[G]: a negative entry leaves that board out.  Returns
+    actions int32[G] (-1: full board or left out), or (actions, scores int64[G,S*S]) with ``scores`` (-1 for an
+    occupied cell)."""
+    L = _lib.load()
+    b = torch.as_tensor(boards).contiguous()
+    if b.dtype != torch.int8 or b.dim() < 2:
+        raise ValueError("anchor_move: boards must be int8 [G, S, S]")
+    G, S = b.shape[0], b.shape[-1]
+    p = torch.as_tensor(players, dtype=torch.int8).to(b.device).contiguous()
+    nz = None if noise is None else torch.as_tensor(noise, dtype=torch.float64).to(b.device).contiguous()
+    gm = None if game is None else torch.as_tensor(game, dtype=torch.int32).to(b.device).contiguous()
+    if b.numel() != G * S * S or p.numel() != G or (gm is not None and gm.numel() != G):
+        raise ValueError("anchor_move: expected boards [G, S, S] with players (and game) of G entries")
+    act = torch.empty(G, dtype=torch.int32, device=b.device)
+    sc = torch.empty(G, S * S, dtype=torch.int64, device=b.device) if scores else None
+    check(L.gmz_game_anchor_move(ptr(b), ptr(p), ptr(gm), ptr(nz), _lib.nbytes(nz), G, S, int(n_in_row),
+                                 anchor_kind(kind), float(scale), ptr(act), _lib.nbytes(act), ptr(sc), _lib.nbytes(sc),
+                                 _lib.stream_ptr(stream)))
+    return (act, sc) if scores else act
 
 
 def _has_five(board, n_in_row=5):

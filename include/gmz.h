@@ -254,6 +254,25 @@ int gmz_engine_play_refill(gmz_engine *e, const int32_t *action_dev, int8_t *sta
 int gmz_gumbel_keyed(const uint32_t *keys_dev, const uint32_t *plies_dev, uint64_t seed, int G, int A, double *out_dev,
                      size_t out_bytes, void *stream);
 
+/* The move of a fixed, non-network anchor opponent for the player to move (players_dev[g]) on G boards, in one
+ * launch (additive, ABI stays 10).  Score of an empty cell c, an int64: over each side s in (p, -p), each direction
+ * (0,1), (1,0), (1,1), (1,-1) and each offset o = 0..n_in_row-1, the window of n_in_row cells that holds c at
+ * index o counts if it lies on the board and holds no stone of -s; with k stones of s in it and
+ * m = n_in_row - 1 - k, it adds W_own[min(m, 4)] = {2^26, 2^13, 2^6, 2^2, 1} for s = p and W_opp[min(m, 4)] =
+ * {2^20, 2^10, 2^5, 2^1, 0} for s = -p.  kind 0 (threat) uses these scores, kind 1 (uniform) scores every empty
+ * cell 0.  The move is the empty cell with the largest (key, noise, -cell) compared lexicographically, key =
+ * (double)score + scale * noise (IEEE double, no contraction); noise_dev f64[G][A] or NULL = 0.  actions_dev
+ * int32[G]: the move, -1 on a full board and for a game whose game_dev[g] is negative (game_dev int32[G] or NULL:
+ * gmz_engine_play_refill's slot_game_dev, an idle arena slot).  scores_dev (nullable) int64[G][A]: the score, -1
+ * for an occupied cell and for every cell of a game left out by game_dev.  Refused before any launch, with nothing
+ * written: G < 1, size < 1 or size^2 > 512, n_in_row outside [1, size], kind not 0 or 1, scale negative or not
+ * finite, null boards, players or actions, noise_bytes < G * A * 8 (with noise), actions_bytes < G * 4,
+ * scores_bytes < G * A * 8 (with scores). */
+int gmz_game_anchor_move(const int8_t *boards_dev, const int8_t *players_dev, const int32_t *game_dev,
+                         const double *noise_dev, size_t noise_bytes, int G, int size, int n_in_row, int kind,
+                         double scale, int32_t *actions_dev, size_t actions_bytes, int64_t *scores_dev,
+                         size_t scores_bytes, void *stream);
+
 /* ------------------------------------------------------------------ HashNet test network */
 /* Deterministic integer-hash network (definition: oracle/hashnet.py) used for tree parity.
  * Hidden state = uint32 id per slot in hid_pool_dev[G*slots].

@@ -1,8 +1,9 @@
-"""Arena throughput: moves/s of arena.Arena in its steady state (every slot busy), one network against itself, at
-the headline's shape (15x15, 400 simulations, 1,024 slots, 8 blocks, fp16) — to set beside ``python bench.py``'s
-self-play headline on the same GPU (profiles/arena.txt).
+"""Arena throughput: moves/s of arena.Arena in its steady state (every slot busy), one network against itself or
+against an anchor opponent, at the headline's shape (15x15, 400 simulations, 1,024 slots, 8 blocks, fp16) — to set
+beside ``python bench.py``'s self-play headline on the same GPU (profiles/arena.txt, profiles/arena_anchor.txt).
 
-  python tools/arena_bench.py [--streams 1,2 --steps 10 --warmup 3 --rounds 2]
+  python tools/arena_bench.py [--streams 1,2 --steps 10 --warmup 3 --rounds 2] [--b anchor:threat]
+  python tools/arena_bench.py --anchor-launch 200      (the anchor launch alone, by event timing)
 
 The book holds more openings than the timed plies can finish, so no slot idles; a move is counted from the
 statuses (arena's ``moves_played``).  Prints one JSON line per (round, streams)."""
@@ -21,11 +22,13 @@ from datou_gomoku_muzero_amd import arena as AR, engine as E, network as N, weig
 from datou_gomoku_muzero_amd.config import GmzConfig  # noqa: E402
 
 
-def measure(cfg, sd, slots, streams, steps, warmup, precision, seed):
+def measure(cfg, sd, slots, streams, steps, warmup, precision, seed, side_b="self"):
+    anchor = AR.anchor_from_name(side_b)
     nets = [N.GomokuNetHip(sd, cfg, num_slots=E.hidden_slots(cfg, slots), max_rows=slots, precision=precision)
-            for _ in range(2)]
+            for _ in range(1 if anchor else 2)]
+    # 8 games per slot: against the threat anchor a game lasts some 8 plies, so the default 13 plies finish fewer
     book = AR.paired_openings(4 * slots, cfg.BOARD_SIZE, seed)
-    ar = AR.Arena(cfg, nets[0], nets[1], slots, book, seed=seed, streams=streams)
+    ar = AR.Arena(cfg, nets[0], anchor or nets[1], slots, book, seed=seed, streams=streams)
     ar.start()
     for _ in range(warmup):
         ar.step()
@@ -37,10 +40,33 @@ def measure(cfg, sd, slots, streams, steps, warmup, precision, seed):
     ar.join()
     dt = time.perf_counter() - t0
     moves = sum(e.moves_played for e in ar.engines) - m0
-    out = dict(streams=streams, slots=slots, steps=steps, moves=moves, seconds=round(dt, 4),
+    out = dict(b=side_b, streams=streams, slots=slots, steps=steps, moves=moves, seconds=round(dt, 4),
                moves_per_s=round(moves / dt, 1), finished=int(ar.match.finished[0]),
                waves_last=[e.waves_last for e in ar.engines])
     ar.close()
+    return out
+
+
+def anchor_launch(size, boards, reps, seed):
+    """Microseconds per gmz_game_anchor_move launch on ``boards`` mid-game boards, by HIP events over ``reps``
+    launches (threat rule with Gumbel noise, and the uniform rule)."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    b, p, _, _ = E.random_openings(boards, size, rs, 60)
+    b, p = torch.from_numpy(b).cuda(), torch.from_numpy(p).cuda()
+    noise = torch.from_numpy(rs.gumbel(0, 1, (boards, size * size))).cuda()
+    out = dict(size=size, boards=boards, reps=reps)
+    for kind, scale in (("threat", 0.0), ("uniform", 1.0)):
+        for _ in range(10):
+            E.anchor_move(b, p, noise, kind, scale)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(reps):
+            E.anchor_move(b, p, noise, kind, scale)
+        ev[1].record()
+        torch.cuda.synchronize()
+        out["us_per_launch_" + kind] = round(1000.0 * ev[0].elapsed_time(ev[1]) / reps, 2)
     return out
 
 
@@ -56,12 +82,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--b", default="self", help="side B: 'self' (the network against itself), anchor:threat or "
+                                                "anchor:uniform")
+    ap.add_argument("--anchor-launch", type=int, default=0, metavar="REPS",
+                    help="time the anchor launch alone on --slots boards over REPS launches, and stop")
     a = ap.parse_args()
+    if a.anchor_launch:
+        print(json.dumps(anchor_launch(a.size, a.slots, a.anchor_launch, a.seed)), flush=True)
+        return
     cfg = GmzConfig(BOARD_SIZE=a.size, NUM_SIMULATIONS=a.sims, NUM_RES_BLOCKS=a.blocks)
     sd = W.synthetic_state_dict(cfg, seed=a.seed, with_projection=False)
     for r in range(a.rounds):
         for s in [int(x) for x in a.streams.split(",")]:
-            out = measure(cfg, sd, a.slots, s, a.steps, a.warmup, a.precision, a.seed)
+            out = measure(cfg, sd, a.slots, s, a.steps, a.warmup, a.precision, a.seed, a.b)
             out["round"] = r
             print(json.dumps(out), flush=True)
 
