@@ -102,8 +102,8 @@ def discount_table(cfg):
 
 
 def static_input_spec(cfg, B):
-    """The trainer's seven static inputs for a batch of ``B`` as (name, dtype, shape): what Trainer.step_from
-    allocates, gmz_replay_gather writes and Trainer._augment_into_static's copies imply."""
+    """The trainer's seven static inputs for a batch of ``B`` as (name, dtype, shape): what Trainer._prepare
+    allocates and gmz_replay_gather or Trainer._augment_into_static's copies write."""
     U, H = int(cfg.NUM_UNROLL_STEPS), int(cfg.BOARD_SIZE)
     f32, i64 = torch.float32, torch.int64
     return (("observations", f32, (B, U + 1, 3, H, H)), ("actions", i64, (B, U)), ("rewards", f32, (B, U)),

@@ -26,6 +26,7 @@ trunks' first convolutions, 1x1 convolutions and Linears run on MIOpen / hipBLAS
 """
 import collections
 import contextlib
+import ctypes
 import math
 from dataclasses import dataclass, field, asdict
 
@@ -33,6 +34,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _lib  # loads nothing until _lib.load(): importing this module needs no libgmz.so
 
 
 @dataclass
@@ -243,7 +246,6 @@ class _FusedMaskedBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, res, mask, running_mean, running_var, num_batches, eps, momentum, relu,
                 stats=None, link=None, bwd_link=False, defer=False):
-        from . import _lib
         layout = _bn_layout(x)
         if layout is None:
             x, layout = x.contiguous(), 0
@@ -289,7 +291,6 @@ class _FusedMaskedBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import _lib
         x, y, mask, gamma, save = ctx.saved_tensors
         layout = ctx.layout
         dy = _like(dy, layout)
@@ -335,7 +336,6 @@ class _FusedMaskedBN(torch.autograd.Function):
 
 
 def _bn_workspace(layout, B, C, S, device):
-    from . import _lib
     n = _lib.query("gmz_bn_workspace_bytes", layout, B, C, S)
     return torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
 
@@ -377,7 +377,6 @@ def _bn_seg(mod, x, mask, res, relu, nseg):
     """Training-mode BatchNorm (+ res, ReLU) of ``nseg`` equal row segments of a channels-last activation in one
     pass (``gmz_bn_forward_seg``): segment statistics from the producing conv's per-board partials when it left
     them (``_conv3_apply`` with segments), else one reduction pass; no autograd (no_grad callers only)."""
-    from . import _lib
     B, C = x.shape[0], x.shape[1]
     S = x[0, 0].numel()
     if res is not None:
@@ -397,7 +396,6 @@ def _bn_seg(mod, x, mask, res, relu, nseg):
 def _bn_eval(mod, x, res, relu):
     """Eval-mode BatchNorm (running statistics) + residual + ReLU as one HIP pass (``gmz_bn_eval``):
     the target network's fp32 forward (loss.py:54-55), no autograd."""
-    from . import _lib
     layout = _bn_layout(x)
     if res is not None:
         res = _like(res.to(x.dtype), layout)
@@ -489,7 +487,6 @@ def _packed_conv_weight(w, dtype, transpose, parent=None):
     parameter per (dtype, transpose) and its version counter, so a weight used by several unroll
     steps is packed once per optimiser step (also inside a captured step: first use packs).  ``parent``: w is
     the view W[:, :128] of that larger parameter (the dynamics stem), cached on it."""
-    from . import _lib
     owner = w if parent is None else parent
     key = (dtype, transpose) if parent is None else ("stem", dtype, transpose)
     cache = owner.__dict__.setdefault("_gmz_pack", {})
@@ -519,7 +516,6 @@ def _packed_split_weight(w):
     """gmz_conv3x3_pack_split of ``w`` (f32 [128,128,3,3], any memory format): [hi fragments | lo fragments], cached
     on the parameter per version counter under its own attribute (``_gmz_pack`` holds the f16/bf16 packs, which
     _repack_stale and the tests read as 5-tuples with a dtype)."""
-    from . import _lib
     hit = w.__dict__.get("_gmz_pack_split")
     if hit is not None and hit[0] == w._version:
         return hit[1]
@@ -533,7 +529,6 @@ def _packed_split_weight(w):
 def _conv3x3_split_hip(x, packed, bn=None, res=None, relu=False):
     """gmz_conv3x3_forward_split of the float32 channels-last x; ``bn``: the eval-mode BatchNorm (+ ``res``, ReLU)
     applied in the kernel's epilogue."""
-    from . import _lib
     y = torch.empty_like(x, memory_format=torch.channels_last)
     if bn is None:
         if res is not None or relu:
@@ -556,7 +551,6 @@ def _repack_stale(owners, tables, prepare=False):
     then current, so the step's forward and backward find them packed.  ``tables``: the device job tables by content
     (a captured step replays the one it was captured with; inside a capture only an existing table is used — an
     unseen set of stale weights is left to the per-use packs; ``prepare``: only build the tables, before a capture)."""
-    from . import _lib
     jobs = {}
     for owner in owners:
         cache = owner.__dict__.get("_gmz_pack")
@@ -611,7 +605,6 @@ def _conv3x3_hip(x, packed, mask=None, stats=None, addend=None, bnb=None, bn_y=N
     """``bnb``: a _BnBwdLink whose BatchNorm output ``bn_y`` fed the forward conv: the output (its dy) also
     gets that BatchNorm's backward dz sums, returned as ``bnb.bwd``.  ``pend``: x is a deferred BatchNorm output
     (_PendingBN), applied and written by this conv's prologue."""
-    from . import _lib
     y = torch.empty_like(x, memory_format=torch.channels_last)
     dt, H, N, stream = _CONV_DTYPES[x.dtype], x.shape[2], x.shape[0], _lib.stream_ptr()
     if pend is not None:
@@ -674,8 +667,6 @@ _PENDING_WGRAD = {}
 
 def flush_wgrads():
     """Run the deferred weight gradients (DEFER_WGRAD) into their parameters' f32 .grad."""
-    import ctypes
-    from . import _lib
     for w, uses in _PENDING_WGRAD.items():
         groups = {}
         for x, gy in uses:
@@ -692,15 +683,39 @@ def flush_wgrads():
     _PENDING_WGRAD.clear()
 
 
+@contextlib.contextmanager
+def _own_backward(keep_pending=False):
+    """Trainer's own backward or deferred weight-gradient pass: _DIRECT_GRAD is set inside; on the way out it is
+    reset and the deferred weight gradients are dropped — a failed pass must not leave its activations queued for
+    the next one — unless ``keep_pending`` and the body succeeded (bucket B stays queued for ``flush_wgrads``)."""
+    _DIRECT_GRAD[0] = True
+    ok = False
+    try:
+        yield
+        ok = True
+    finally:
+        _DIRECT_GRAD[0] = False
+        if not (keep_pending and ok):
+            _PENDING_WGRAD.clear()
+
+
+def _draw_augmentation(k=None, flip=None):
+    """The batch's augmentation: an argument that is None is drawn from numpy's global RandomState, the quarter
+    turns first and the flip second (the reference's order, loss.py:37-38)."""
+    if k is None:
+        k = np.random.randint(4)
+    if flip is None:
+        flip = bool(np.random.choice([True, False]))
+    return k, flip
+
+
 def _wgrad_workspace(boards, device):
-    from . import _lib
     nb = _lib.query("gmz_conv3x3_wgrad_workspace_bytes", boards)
     return torch.empty(nb // 4, dtype=torch.float32, device=device)
 
 
 def _conv3x3_wgrad_hip(x, gy, grad):
     """grad (f32, any strides) += weight gradient of the 128->128 conv from channels-last x, gy."""
-    from . import _lib
     N = x.shape[0]
     ws = _wgrad_workspace(N, x.device)
     _lib.call("gmz_conv3x3_wgrad", _CONV_DTYPES[x.dtype], x.shape[2], x, gy, N, grad, *grad.stride(), 1, ws,
@@ -709,8 +724,6 @@ def _conv3x3_wgrad_hip(x, gy, grad):
 
 def _conv_stats_buffer(N, device):
     """f64 [128][slots][3] partials (channel-major) for gmz_conv3x3_forward_stats -> (tensor, slots)."""
-    import ctypes
-    from . import _lib
     ns = _lib.query("gmz_conv3x3_stats_slots", N, ctype=ctypes.c_int)
     return torch.empty(ns * 128 * 3, dtype=torch.float64, device=device), ns
 
@@ -796,7 +809,6 @@ class _DynStemHIP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, W, w_emb, a, mask, stats):
-        from . import _lib
         dt = h.dtype
         n, _, H, _ = h.shape
         # the table in float32 whatever the caller's autocast state (under autocast einsum would run in f16 and
@@ -890,7 +902,6 @@ def _conv3_apply(conv, x, bn=None, mask=None, link=None, segments=1):
     ``segments`` > 1 (no_grad only): the statistics partials per board, for the segmented BatchNorm."""
     dt = _hip_conv_dtype(conv, x)
     if dt is not None and segments > 1 and not torch.is_grad_enabled():
-        from . import _lib
         xin = x.to(dt)
         N, H = xin.shape[0], xin.shape[2]
         y = torch.empty_like(xin, memory_format=torch.channels_last)
@@ -987,7 +998,6 @@ FUSED_HEADS = True
 def _headconv_forward(x, w0, b0, w1, b1):
     """gmz_head_conv1x1_forward of the channels-last x: (y0, y1) channels-last [n, O, H, W] and what the backward
     needs"""
-    from . import _lib
     n, C, H, W = x.shape
     O0, O1 = w0.shape[0], w1.shape[0]
     P = n * H * W
@@ -1002,7 +1012,6 @@ def _headconv_forward(x, w0, b0, w1, b1):
 def _headconv_backward(x, saved, params, g0, g1):
     """gmz_head_conv1x1_backward: (dx channels-last like x, the four parameter gradients — None when they went
     straight into the trainer's f32 .grad, _DIRECT_GRAD)"""
-    from . import _lib
     w0m, w1m, (O0, O1) = saved
     n, C, H, W = x.shape
     P = n * H * W
@@ -1189,7 +1198,6 @@ class _BigKLinear(torch.autograd.Function):
             else:
                 # W's (c, p) column order, added straight into the f32 .grad by an LDS-tiled transpose
                 # (gmz_grad_add_t: 109 -> ~45 us per call vs a strided PyTorch add at 512 x 28,800)
-                from . import _lib
                 C, HW = ctx.perm
                 dst = w.grad if acc else torch.zeros(w.shape, dtype=torch.float32, device=w.device)
                 _lib.call("gmz_grad_add_t", _BN_DTYPES[gwt.dtype], gwt, HW, C, O, dst, _lib.stream_ptr())
@@ -1250,7 +1258,6 @@ def _bigk2_backward(xs, ws, w1, w2, perm, g1, g2, needs, gx_acc=None):
             if perm is None:
                 outs[2 * i] = gwt[:, c0:c0 + O].t().to(w.dtype)
                 continue
-            from . import _lib
             C, HW = perm
             dst = w.grad if acc else torch.zeros(w.shape, dtype=torch.float32, device=w.device)
             _lib.call("gmz_grad_add_t_cols", _BN_DTYPES[gwt.dtype], gwt, HW, C, O, O1 + O2, c0, dst, _lib.stream_ptr())
@@ -1622,7 +1629,6 @@ _SEG_BN_SMALL_C = 8
 
 
 def _seg_bn_small_ws(nseg, C, device):
-    from . import _lib
     n = _lib.query("gmz_seg_bn_small_workspace_bytes", nseg, C)
     return torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
 
@@ -1633,7 +1639,6 @@ class _SegBN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, m, nseg, eps, update, momentum, rmean, rvar, nbt, pre):
-        from . import _lib
         N, C = x.shape[0], x.shape[1]
         S = x[0, 0].numel() if x.dim() > 2 else 1
         if x.dim() == 4:
@@ -1655,7 +1660,6 @@ class _SegBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gst):
-        from . import _lib
         x, gamma, beta, st, m = ctx.saved_tensors
         N, C = x.shape[0], x.shape[1]
         S = x[0, 0].numel() if x.dim() > 2 else 1
@@ -1983,11 +1987,7 @@ def muzero_loss(model, target_model, batch, is_weights, cfg, k=None, flip=None, 
     if augmented:
         act_aug = batch[5]
     else:
-        if k is None:
-            k = np.random.randint(4)
-        if flip is None:
-            flip = bool(np.random.choice([True, False]))
-        obs, pi, act_aug = augment(obs, pi, act, k, flip)
+        obs, pi, act_aug = augment(obs, pi, act, *_draw_augmentation(k, flip))
     model.train()
     target_model.eval()
     c, W, U = cfg, cfg.LOSS_WEIGHTS, cfg.NUM_UNROLL_STEPS
@@ -2039,6 +2039,98 @@ from .replay import ReplayBuffer, RingGame, static_input_spec  # noqa: E402,F401
 
 
 # ------------------------------------------------------------------------------ trainer
+def _soft_update(pairs, tau):
+    """utils.py:28-31 on (target, model) parameter pairs: t = (1 - tau) * t + tau * p, by fused foreach kernels, which
+    need equal strides within a call (an NCHW target beside an NHWC model)."""
+    with torch.no_grad():
+        for same in (True, False):
+            tp = [t for t, p in pairs if (t.stride() == p.stride()) == same]
+            sp = [p for t, p in pairs if (t.stride() == p.stride()) == same]
+            if tp:
+                torch._foreach_mul_(tp, 1.0 - tau)
+                torch._foreach_add_(tp, sp, alpha=tau)
+
+
+class _FusedOpt:
+    """FUSED_OPT's state: gmz_opt_step's work items over the gradient bucket, the Adam moments ``m``, ``v`` as
+    bucket-shaped buffers and one step count ``steps`` (torch's optimiser state becomes views of them, so state_dict /
+    load_state_dict keep the reference's format) and the target twins (a parameter whose twin has other strides gets
+    its soft update from PyTorch).  Building it copies from the host and fills buffers, so it is built outside any
+    graph capture (Trainer._prepare)."""
+
+    @staticmethod
+    def supports(opt, params, device):
+        g = opt.param_groups[0]
+        return (device.type == "cuda" and len(opt.param_groups) == 1 and torch.is_tensor(g["lr"])
+                and not g.get("amsgrad") and not g.get("maximize") and all(p.dtype == torch.float32 for p in params))
+
+    def __init__(self, params, flat_grad, opt, pairs):
+        """``pairs``: the (target, model) parameter pairs of the soft update."""
+        ib, ch, wsb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_size_t()
+        _lib.call("gmz_opt_layout", ctypes.byref(ib), ctypes.byref(ch), ctypes.byref(wsb))
+        dt = np.dtype([("p", "<u8"), ("t", "<u8"), ("off", "<i8"), ("n", "<i4"), ("pi", "<i4")])
+        if ib.value != dt.itemsize:
+            raise _lib.GmzError("gmz_opt_layout: item of %d bytes, expected %d" % (ib.value, dt.itemsize))
+        device = flat_grad.device
+        twin = {id(p): t for t, p in pairs}
+        self.params, self.opt, self.flat_grad = params, opt, flat_grad
+        self.m, self.v = torch.zeros_like(flat_grad), torch.zeros_like(flat_grad)
+        self.steps = torch.zeros((), dtype=torch.float32, device=device)
+        base, items, self.fallback = flat_grad.data_ptr(), [], []
+        for p in params:
+            n = p.numel()
+            off = (p.grad.data_ptr() - base) // 4
+            dense = p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last)
+            if not (dense and p.grad.stride() == p.stride() and 0 <= off and off + n <= flat_grad.numel()):
+                raise RuntimeError("Trainer: a parameter's gradient is not its bucket range in its own layout")
+            t = twin.get(id(p))
+            t_ok = t is not None and t.is_cuda and t.dtype == torch.float32 and t.stride() == p.stride()
+            if t is not None and not t_ok:
+                self.fallback.append((t, p))
+            for i0 in range(0, n, ch.value):
+                items.append((p.data_ptr(), t.data_ptr() if t_ok else 0, off + i0, min(ch.value, n - i0), i0))
+            mv = self.m[off:off + n].as_strided(p.shape, p.stride())
+            vv = self.v[off:off + n].as_strided(p.shape, p.stride())
+            st = opt.state.get(p)
+            if st:  # resumed or earlier PyTorch steps: the moments and the step carry over
+                mv.copy_(st["exp_avg"])
+                vv.copy_(st["exp_avg_sq"])
+                self.steps.copy_(torch.as_tensor(st["step"], dtype=torch.float32))
+            opt.state[p] = {"step": self.steps, "exp_avg": mv, "exp_avg_sq": vv}
+        self.items = torch.from_numpy(np.array(items, dtype=dt).view(np.uint8)).to(device)
+        self.n_items = len(items)
+        self.coef = torch.zeros(2, dtype=torch.float32, device=device)
+        self.ws = torch.zeros((wsb.value + 7) // 8, dtype=torch.float64, device=device)
+        self.versioned = list(params) + [twin[id(p)] for p in params if id(p) in twin]
+
+    def step(self, scaler, cfg):
+        """Unscale + clip + Adam + soft update + zero_grad in three launches, then GradScaler.update with the step's
+        found_inf and PyTorch's soft update of the ``fallback`` pairs."""
+        g = self.opt.param_groups[0]
+        amp = scaler.is_enabled()
+        b1, b2 = g["betas"]
+        _lib.call("gmz_opt_step", self.items, self.n_items, self.flat_grad, self.m, self.v, self.flat_grad.numel(),
+                  scaler._scale if amp else None, int(amp), float(cfg.GRAD_CLIP_NORM), g["lr"], float(b1), float(b2),
+                  float(g["eps"]), float(g["weight_decay"]), float(cfg.TARGET_MODEL_TAU), self.steps, self.coef,
+                  self.ws, _lib.nbytes(self.ws), _lib.stream_ptr())
+        if amp:
+            torch._amp_update_scale_(scaler._scale, scaler._growth_tracker, self.coef[:1], scaler._growth_factor,
+                                     scaler._backoff_factor, scaler._growth_interval)
+        # the kernel wrote the parameters through raw pointers: advance their version counters as PyTorch's
+        # in-place update would, so the packed-weight caches keyed on them (_packed_conv_weight, _bigk_weight)
+        # re-pack — and a graph capture after this step records the packs
+        torch.autograd.graph.increment_version(self.versioned)
+        self.opt._opt_called = True  # what Optimizer.step records for the LR scheduler's call-order check
+        _soft_update(self.fallback, cfg.TARGET_MODEL_TAU)
+
+    def release(self):
+        """Back to PyTorch's optimiser after fused steps: one step tensor per parameter again (the moments stay the
+        views they are)."""
+        for p in self.params:
+            st = self.opt.state[p]
+            st["step"] = st["step"].clone()
+
+
 class Trainer:
     """training_worker's step (workers.py:452-463, 556-584) without the queues: Adam with weight
     decay, LinearLR warm-up (1000 updates) then cosine annealing to 1e-7 over 200k updates, AMP
@@ -2052,7 +2144,13 @@ class Trainer:
     ``graph=True`` (default on cuda, GRADIENT_ACCUMULATION_STEPS == 1) the whole step — target-net
     bootstrap, loss, backward, unscale, clip, Adam, scale update, soft target update — is captured
     once into a HIP graph and replayed (distributed: with the RCCL all-reduces inside it).  The
-    batch is augmented eagerly into static input buffers before each replay.  The first ``graph_warmup`` steps run eagerly (they are real steps)."""
+    batch is augmented eagerly into static input buffers before each replay.
+
+    Lifecycle of a step: every step first calls ``_prepare``, the one place that builds the state a
+    step finds ready — the fused optimiser's buffers, the static inputs, the GradScaler's tensors, before a capture
+    the re-pack job tables — always outside a capture, so a captured step holds the step's kernels and nothing that
+    builds state.  The first ``graph_warmup`` steps of THIS object run eagerly (they are real steps), whatever
+    ``step_count`` a checkpoint brought; ``load_trainer_state`` starts the count again (``_invalidate``)."""
 
     def __init__(self, cfg=None, device="cuda", state_dict=None, amp=None, amp_dtype=None, channels_last=None,
                  graph=None, graph_warmup=3):
@@ -2115,73 +2213,98 @@ class Trainer:
             torch.optim.lr_scheduler.LinearLR(self.opt, start_factor=0.01, total_iters=warm),
             torch.optim.lr_scheduler.CosineAnnealingLR(self.opt, T_max=total - warm, eta_min=1e-7)], milestones=[warm])
         self.scaler = torch.amp.GradScaler(self.device.type, enabled=self.amp and amp_dtype in (None, torch.float16))
-        self.step_count = 0
+        self.step_count = 0  # the checkpoint's train_step_count, and the gradient-accumulation phase
         self.graph = (cuda and acc == 1) if graph is None else (bool(graph) and cuda and acc == 1)
-        self.graph_warmup = max(1, int(graph_warmup))  # eager steps first: lazy AMP/optimiser state
-        self._graphs = None  # the captured step: a CUDAGraph, or (step, flush, update) graphs (see _capture)
-        self._fopt = None  # FUSED_OPT's buffers (built at the first update)
-        self.graph_allreduce = False  # True once the captured step holds the RCCL all-reduces
-        self._static = None
+        # eager steps THIS object takes before it captures (counted down in _warmup_left, not read off step_count):
+        # what is lazy below the trainer — MIOpen's algorithm search, the packed-weight and workspace caches, the
+        # allocator's pools — fills outside the graph; the step's own state is _prepare's, not the warm-up's
+        self.graph_warmup = max(1, int(graph_warmup))
         self._pack_tables = {}  # BATCH_REPACK's job tables
+        self._invalidate()
+
+    # ------------------------------------------------------------------ the step's state
+    def _invalidate(self):
+        """Forget everything ``_prepare`` and ``_capture`` build: the next step prepares again and the warm-up
+        starts over (construction; a loaded checkpoint replaced the tensors the old state pointed into)."""
+        self._graphs = None  # the captured step: a CUDAGraph, or (step, flush, update) graphs (see _capture)
+        self._out = None  # the captured step's (logs, td) outputs
+        self.graph_allreduce = False  # True once the captured step holds the RCCL all-reduces
+        self._static = None  # the captured step's inputs (replay.static_input_spec)
+        self._fopt = None  # the _FusedOpt; it adopts the optimiser's moments and step when built
+        self._warmup_left = self.graph_warmup  # eager steps still to take before the capture
+        # whether this optimiser can take the fused step at all: read here (a loaded checkpoint brings its own
+        # param_groups), not walked over the parameters at every step
+        self._fusable = _FusedOpt.supports(self.opt, self.params, self.device)
+
+    def _fused_opt_ok(self):
+        return FUSED_OPT and self._fusable
+
+    def _graph_due(self):
+        return self.graph and self._warmup_left == 0
+
+    def _prepare(self, B=None):
+        """Everything a step needs that is not the step's own work, built here and never inside a capture; every
+        step calls it before its forward, and once built it is a few flag checks.  The fused optimiser's buffers
+        when FUSED_OPT applies (handed back to PyTorch's optimiser when it no longer does: tools and tests toggle the
+        flag between steps); the GradScaler's scale and growth tracker (its own lazy initialisation, which the first
+        ``scale()`` would otherwise run inside the step; the scale keeps its value); with ``B``, the static inputs for
+        a batch of B (a graph step, or ``step_from``); before a capture, BATCH_REPACK's job tables for the weights
+        the captured step will find stale."""
+        if self._fused_opt_ok() != (self._fopt is not None):
+            if self._fopt is None:
+                pairs = list(zip(self.target.parameters(), self.model.parameters()))
+                self._fopt = _FusedOpt(self.params, self.flat_grad, self.opt, pairs)
+            else:
+                self._fopt.release()
+                self._fopt = None
+        if self.scaler.is_enabled() and self.scaler._scale is None:
+            self.scaler._lazy_init_scale_growth_tracker(self.device)
+        if B is not None and self._static is None:
+            self._static = tuple(torch.empty(shape, dtype=dt, device=self.device)
+                                 for _, dt, shape in static_input_spec(self.cfg, B))
+        if self._graphs is None and self._graph_due() and BATCH_REPACK:
+            _repack_stale(list(self.model.parameters()) + list(self.target.parameters()), self._pack_tables,
+                          prepare=True)
 
     # ------------------------------------------------------------------ step pieces
     def _forward_backward(self, batch, is_weights, acc=1, k=None, flip=None, augmented=False, flush=True):
         """Loss and backward; ``flush`` = False leaves the deferred 3x3 weight gradients queued (bucket B) for
-        ``flush_wgrads`` after bucket A's all-reduce has been issued."""
+        ``_flush`` after bucket A's all-reduce has been issued."""
         if BATCH_REPACK and self.device.type == "cuda":
             _repack_stale(list(self.model.parameters()) + list(self.target.parameters()), self._pack_tables)
         loss, logs, td = muzero_loss(self.model, self.target, batch, is_weights, self.cfg, k=k, flip=flip,
                                      amp=self.amp, amp_dtype=self.amp_dtype, sync_logs=False, augmented=augmented)
-        _DIRECT_GRAD[0] = True
-        ok = False
-        try:
+        with _own_backward(keep_pending=not flush):
             self.scaler.scale(loss / acc).backward()
             if flush:
                 flush_wgrads()
-            ok = True
-        finally:
-            _DIRECT_GRAD[0] = False
-            if flush or not ok:
-                _PENDING_WGRAD.clear()
         return logs, td
 
     def _flush(self):
-        try:
+        with _own_backward():
             flush_wgrads()
-        finally:
-            _PENDING_WGRAD.clear()
 
     def _stamp(self, phase):
         if self._comm_clock is not None:
-            from . import _lib
             _lib.call("gmz_comm_stamp", self._comm_clock, phase, _lib.stream_ptr())
 
-    def _allreduce_start(self):
-        """Bucket A's all-reduce, issued asynchronously (RCCL on its own stream, after the backward's kernels)."""
-        if self.dist is None:
-            return None
-        self._stamp(0)
-        return self.dist.all_reduce(self.flat_grad[:self._bucket_a], async_op=True)
-
-    def _mark_flushed(self):
-        """Bucket B's weight gradients are enqueued (the compute stream's work between A's issue and B's)."""
-        self._stamp(1)
-
-    def _allreduce_finish(self, work):
-        """Bucket B's all-reduce (its gradients are final once flush_wgrads ran), then both buckets averaged."""
+    def _reduce_gradients(self, flush):
+        """Data parallel (a no-op without a process group): the two buckets' all-reduces (RCCL), overlapped with the
+        deferred weight gradients.  Bucket A's is issued asynchronously (RCCL on its own stream, after the backward's
+        kernels); ``flush()`` enqueues bucket B's weight gradients beside it (``self._flush``, or the replay of the
+        graph that holds it); then B's all-reduce (its gradients are final once the flush ran), A's wait, and both
+        buckets averaged.  The gmz_comm_stamp phases 0, 1, 2 around them are what ``allreduce_times`` reads."""
         if self.dist is None:
             return
+        self._stamp(0)
+        work = self.dist.all_reduce(self.flat_grad[:self._bucket_a], async_op=True)
+        flush()
+        self._stamp(1)
         if self._bucket_a < self.flat_grad.numel():
             self.dist.all_reduce(self.flat_grad[self._bucket_a:])
         work.wait()
         self.flat_grad.div_(self.dist.get_world_size())
         self._stamp(2)
-
-    def _allreduce(self):
-        if self.dist is not None:  # data parallel: the two buckets' all-reduces (RCCL), A's issued first
-            work = self._allreduce_start()
-            self._mark_flushed()
-            self._allreduce_finish(work)
 
     def allreduce_times(self):
         """Mean per-step times (ms) on the compute stream since construction or ``reset_allreduce_times`` (GPU with a
@@ -2206,114 +2329,34 @@ class Trainer:
         t = self.allreduce_times()
         return None if t is None else t["wait_ms"]
 
-    def _fused_opt_ok(self):
-        g = self.opt.param_groups[0]
-        return (FUSED_OPT and self.device.type == "cuda" and len(self.opt.param_groups) == 1
-                and torch.is_tensor(g["lr"]) and not g.get("amsgrad") and not g.get("maximize")
-                and all(p.dtype == torch.float32 for p in self.params))
-
-    def _fused_opt_setup(self):
-        """gmz_opt_step's work items over the gradient bucket, the Adam moments as bucket-shaped buffers (torch's
-        optimiser state becomes views of them, so state_dict / load_state_dict keep the reference's format) and the
-        target twins (a parameter whose twin has other strides gets its soft update from PyTorch)."""
-        import ctypes
-        from . import _lib
-        ib, ch, wsb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_size_t()
-        _lib.call("gmz_opt_layout", ctypes.byref(ib), ctypes.byref(ch), ctypes.byref(wsb))
-        dt = np.dtype([("p", "<u8"), ("t", "<u8"), ("off", "<i8"), ("n", "<i4"), ("pi", "<i4")])
-        if ib.value != dt.itemsize:
-            raise _lib.GmzError("gmz_opt_layout: item of %d bytes, expected %d" % (ib.value, dt.itemsize))
-        twin = {id(p): t for t, p in zip(self.target.parameters(), self.model.parameters())}
-        m, v = torch.zeros_like(self.flat_grad), torch.zeros_like(self.flat_grad)
-        step = torch.zeros((), dtype=torch.float32, device=self.device)
-        base, items, fallback = self.flat_grad.data_ptr(), [], []
-        for p in self.params:
-            n = p.numel()
-            off = (p.grad.data_ptr() - base) // 4
-            dense = p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last)
-            if not (dense and p.grad.stride() == p.stride() and 0 <= off and off + n <= self.flat_grad.numel()):
-                raise RuntimeError("Trainer: a parameter's gradient is not its bucket range in its own layout")
-            t = twin.get(id(p))
-            t_ok = t is not None and t.is_cuda and t.dtype == torch.float32 and t.stride() == p.stride()
-            if t is not None and not t_ok:
-                fallback.append((t, p))
-            for i0 in range(0, n, ch.value):
-                items.append((p.data_ptr(), t.data_ptr() if t_ok else 0, off + i0, min(ch.value, n - i0), i0))
-            mv = m[off:off + n].as_strided(p.shape, p.stride())
-            vv = v[off:off + n].as_strided(p.shape, p.stride())
-            st = self.opt.state.get(p)
-            if st:  # resumed or earlier PyTorch steps: the moments and the step carry over
-                mv.copy_(st["exp_avg"])
-                vv.copy_(st["exp_avg_sq"])
-                step.copy_(torch.as_tensor(st["step"], dtype=torch.float32))
-            self.opt.state[p] = {"step": step, "exp_avg": mv, "exp_avg_sq": vv}
-        arr = np.array(items, dtype=dt)
-        versioned = list(self.params) + [twin[id(p)] for p in self.params if id(p) in twin]
-        self._fopt = {"items": torch.from_numpy(arr.view(np.uint8)).to(self.device), "n_items": len(items),
-                      "m": m, "v": v, "step": step, "coef": torch.zeros(2, dtype=torch.float32, device=self.device),
-                      "ws": torch.zeros((wsb.value + 7) // 8, dtype=torch.float64, device=self.device),
-                      "fallback": fallback, "versioned": versioned}
-
     def _update(self):
+        """The optimiser step and the soft target update on the state ``_prepare`` left; it builds nothing."""
         c = self.cfg
-        if self._fused_opt_ok():  # FUSED_OPT: unscale + clip + Adam + soft update + zero_grad in three launches
-            from . import _lib
-            if self._fopt is None:
-                self._fused_opt_setup()
-            f, g = self._fopt, self.opt.param_groups[0]
-            amp = self.scaler.is_enabled()
-            scale = self.scaler._scale if amp else None
-            b1, b2 = g["betas"]
-            _lib.call("gmz_opt_step", f["items"], f["n_items"], self.flat_grad, f["m"], f["v"], self.flat_grad.numel(),
-                      scale, int(amp), float(c.GRAD_CLIP_NORM), g["lr"], float(b1), float(b2), float(g["eps"]),
-                      float(g["weight_decay"]), float(c.TARGET_MODEL_TAU), f["step"], f["coef"], f["ws"],
-                      _lib.nbytes(f["ws"]), _lib.stream_ptr())
-            if amp:  # GradScaler.update with the step's found_inf
-                torch._amp_update_scale_(self.scaler._scale, self.scaler._growth_tracker, f["coef"][:1],
-                                         self.scaler._growth_factor, self.scaler._backoff_factor,
-                                         self.scaler._growth_interval)
-            # the kernel wrote the parameters through raw pointers: advance their version counters as PyTorch's
-            # in-place update would, so the packed-weight caches keyed on them (_packed_conv_weight, _bigk_weight)
-            # re-pack — and a graph capture after this step records the packs
-            from torch.autograd.graph import increment_version
-            increment_version(f["versioned"])
-            self.opt._opt_called = True  # what Optimizer.step records for the LR scheduler's call-order check
-            if f["fallback"]:
-                with torch.no_grad():
-                    tp, sp = [t for t, _ in f["fallback"]], [p for _, p in f["fallback"]]
-                    torch._foreach_mul_(tp, 1.0 - c.TARGET_MODEL_TAU)
-                    torch._foreach_add_(tp, sp, alpha=c.TARGET_MODEL_TAU)
+        if self._fused_opt_ok() != (self._fopt is not None):  # a direct call after FUSED_OPT changed
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Trainer._update: the optimiser state is not the one FUSED_OPT asks for; _prepare() "
+                                   "builds it before the step, never inside a graph capture")
+            self._prepare()
+        if self._fopt is not None:  # FUSED_OPT: unscale + clip + Adam + soft update + zero_grad in three launches
+            self._fopt.step(self.scaler, c)
             return
-        if self._fopt is not None:  # back on PyTorch's optimiser after fused steps: one step tensor per parameter again
-            for p in self.params:
-                st = self.opt.state[p]
-                st["step"] = st["step"].clone()
-            self._fopt = None
         self.scaler.unscale_(self.opt)
         torch.nn.utils.clip_grad_norm_(self.params, c.GRAD_CLIP_NORM, foreach=self.device.type == "cuda")
         self.scaler.step(self.opt)
         self.scaler.update()
         self.flat_grad.zero_()
-        with torch.no_grad():  # utils.py:28-31 soft update (parameters only): tau * s + (1 - tau) * t
-            pairs = list(zip(self.target.parameters(), self.model.parameters()))
-            for same in (True, False):  # fused foreach kernels need equal strides (NCHW target, NHWC model)
-                tp = [t for t, p in pairs if (t.stride() == p.stride()) == same]
-                sp = [p for t, p in pairs if (t.stride() == p.stride()) == same]
-                if tp:
-                    torch._foreach_mul_(tp, 1.0 - c.TARGET_MODEL_TAU)
-                    torch._foreach_add_(tp, sp, alpha=c.TARGET_MODEL_TAU)
+        _soft_update(list(zip(self.target.parameters(), self.model.parameters())), c.TARGET_MODEL_TAU)  # parameters only
 
     def _augment_into_static(self, batch, is_weights, k, flip):
         obs, act, rew, pi, mval = batch
-        if k is None:
-            k = np.random.randint(4)
-        if flip is None:
-            flip = bool(np.random.choice([True, False]))
-        o, p, a = augment(obs, pi, act.long(), k, flip)
+        o, p, a = augment(obs, pi, act.long(), *_draw_augmentation(k, flip))
         src = (o, act.long(), rew.float(), p, mval.float(), a, is_weights.float())
-        if self._static is None:
-            self._static = tuple(torch.empty_like(t).contiguous() for t in src)
         for dst, t in zip(self._static, src):
+            # observations and policies arrive as float32, replay.static_input_spec's dtype, from every caller
+            # (ReplayBuffer.sample, the benchmarks, the tests); another dtype is refused, not converted by the copy
+            if t.dtype != dst.dtype:
+                raise TypeError("Trainer.step: a batch member is %s where the static inputs hold %s (observations "
+                                "and policies are float32)" % (t.dtype, dst.dtype))
             dst.copy_(t)
 
     def _capture(self):
@@ -2339,10 +2382,7 @@ class Trainer:
             with torch.cuda.graph(g, stream=s, capture_error_mode=mode):
                 self._out = self._forward_backward(st[:6], st[6], augmented=True, flush=not dp)
                 if in_graph:  # bucket A's all-reduce beside bucket B's weight gradients, inside the graph
-                    work = self._allreduce_start()
-                    self._flush()
-                    self._mark_flushed()
-                    self._allreduce_finish(work)
+                    self._reduce_gradients(self._flush)
                 if not dp or in_graph:
                     self._update()
             if dp and not in_graph:  # bucket B's weight gradients and the update as graphs of their own
@@ -2389,54 +2429,51 @@ class Trainer:
         """One training step -> ((total, policy, value, reward, consistency) floats, td errors [B]).
         ``sync=False``: the five losses stay a device tensor [5] (no host synchronisation, so the host
         can prepare the next step while this one runs; read them with ``.tolist()`` later)."""
-        if self.graph and self.step_count >= self.graph_warmup:
-            self._augment_into_static(batch, is_weights, k, flip)
-            logs, td = self._graph_step()
-        else:
-            logs, td = self._eager_step(batch, is_weights, k, flip)
-        return self._finish_step(logs, td, sync)
+        if not self._graph_due():  # the eager step takes the batch as it is
+            self._prepare()
+            return self._run_step(sync, batch, is_weights, k, flip)
+        self._prepare(batch[0].shape[0])
+        self._augment_into_static(batch, is_weights, k, flip)
+        return self._run_step(sync)
 
     def step_from(self, rb, rng, dist=None, k=None, flip=None, sync=True):
         """One training step on a batch taken from the device ring ``rb`` without leaving HIP -> (logs, td, idx)
         as :meth:`step` returns them plus the ring slots drawn (for ``rb.update_priorities(idx, td)``), or None
         when the shard holds no batch.  The draw is ``rb.sample_indices(PHYSICAL_BATCH_SIZE, rng, dist, hip=True)``;
-        ``k``/``flip`` default to draws from numpy's global RandomState in ``_augment_into_static``'s order; one
-        launch (``rb.gather_into``) writes the augmented batch into the captured step's static inputs, which then
-        runs as in :meth:`step` — a graph replay, or the eager step on those inputs (warm-up, gradient
+        ``k``/``flip`` default to draws from numpy's global RandomState (``_draw_augmentation``, after the ring's
+        draw); one launch (``rb.gather_into``) writes the augmented batch into the captured step's static inputs,
+        which then runs as in :meth:`step` — a graph replay, or the eager step on those inputs (warm-up, gradient
         accumulation, ``graph=False``).  ``step`` and ``step_from`` can be mixed on one trainer."""
-        c = self.cfg
-        got = rb.sample_indices(int(c.PHYSICAL_BATCH_SIZE), rng, dist=dist, hip=True)
+        B = int(self.cfg.PHYSICAL_BATCH_SIZE)
+        got = rb.sample_indices(B, rng, dist=dist, hip=True)
         if got is None:
             return None
         idx, w = got
-        if k is None:
-            k = np.random.randint(4)
-        if flip is None:
-            flip = bool(np.random.choice([True, False]))
-        if self._static is None:  # _augment_into_static's shapes and dtypes
-            self._static = tuple(torch.empty(shape, dtype=dt, device=self.device)
-                                 for _, dt, shape in static_input_spec(c, int(c.PHYSICAL_BATCH_SIZE)))
-        rb.gather_into(self._static, idx, w, k, flip)
-        if self.graph and self.step_count >= self.graph_warmup:
+        self._prepare(B)
+        rb.gather_into(self._static, idx, w, *_draw_augmentation(k, flip))
+        return self._run_step(sync) + (idx,)
+
+    def _run_step(self, sync, batch=None, is_weights=None, k=None, flip=None):
+        """The step on ``batch``, or without one on what ``_static`` holds, already augmented: the captured step once
+        this object's warm-up is over, an eager step until then (and always with ``graph=False``)."""
+        if self._graph_due():
             logs, td = self._graph_step()
         else:
-            logs, td = self._eager_step(self._static[:6], self._static[6], None, None, augmented=True)
-        return self._finish_step(logs, td, sync) + (idx,)
+            if batch is None:
+                logs, td = self._eager_step(self._static[:6], self._static[6], None, None, augmented=True)
+            else:
+                logs, td = self._eager_step(batch, is_weights, k, flip)
+            self._warmup_left = max(0, self._warmup_left - 1)
+        return self._finish_step(logs, td, sync)
 
     def _graph_step(self):
         """The captured step on what ``_static`` holds, capturing first when due."""
         if self._graphs is None:
-            if BATCH_REPACK:  # the job table the captured step will replay, built before the capture
-                _repack_stale(list(self.model.parameters()) + list(self.target.parameters()), self._pack_tables,
-                              prepare=True)
             self._capture()
         if isinstance(self._graphs, tuple):  # collectives not capturable: the all-reduces between replays
             g1, gf, g2 = self._graphs
             g1.replay()
-            work = self._allreduce_start()
-            gf.replay()
-            self._mark_flushed()
-            self._allreduce_finish(work)
+            self._reduce_gradients(gf.replay)
             g2.replay()
         else:
             self._graphs.replay()
@@ -2451,12 +2488,8 @@ class Trainer:
         overlap = self.dist is not None and last
         logs, td = self._forward_backward(batch, is_weights, acc, k=k, flip=flip, augmented=augmented,
                                           flush=not overlap)
-        if overlap:  # bucket A's all-reduce beside bucket B's weight gradients
-            work = self._allreduce_start()
-            self._flush()
-            self._mark_flushed()
-            self._allreduce_finish(work)
         if last:
+            self._reduce_gradients(self._flush)  # bucket A's all-reduce beside bucket B's weight gradients
             self._update()
             self.sched.step()
         return logs, td
@@ -2487,8 +2520,7 @@ class Trainer:
         self.sched.load_state_dict(state["scheduler_state_dict"])
         self.step_count = int(state.get("train_step_count", 0))
         self.games_completed = int(state.get("games_completed_count", 0))
-        self._graphs, self._static = None, None  # re-captured on the next step
-        self._fopt = None  # FUSED_OPT adopts the loaded moments and step at the next update
+        self._invalidate()  # prepared, warmed up and captured again from the next step on
 
     def trainer_state(self, games_completed_count=None):
         """The reference's checkpoint dict (workers.py:594-597), CPU tensors, optimiser state in the

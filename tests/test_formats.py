@@ -166,6 +166,33 @@ def test_reference_trainer_state_resumes(golden, tmp_path):
     assert tr2.opt.param_groups[0]["lr"] == tr.opt.param_groups[0]["lr"]
 
 
+def test_loaded_trainer_state_restarts_the_warmup():
+    """load_trainer_state brings the checkpoint's step_count but not a warmed-up object: the eager steps before a
+    graph capture are counted per Trainer, start again after a load, and the next step runs."""
+    import torch
+    from datou_gomoku_muzero_amd import trainer as T
+    st = F.RecordStore(os.path.join(GOLDEN, "ref_trainer_state.db"))
+    state = st.load_trainer_state()
+    st.close(checkpoint=False)
+    d = np.load(os.path.join(GOLDEN, "train_loss.npz"))
+    batch = [torch.from_numpy(d[k]) for k in ("obs", "act", "rew", "pol", "val")]
+    w = torch.ones(batch[0].shape[0])
+    tr = T.Trainer(T.TrainConfig(BOARD_SIZE=6, NUM_RES_BLOCKS=1, NUM_FILTERS=8), device="cpu", graph_warmup=2)
+    assert tr._warmup_left == 2 and tr.step_count == 0
+    for _ in range(3):
+        tr.step(batch, w, k=0, flip=False)
+    assert tr._warmup_left == 0 and tr.step_count == 3
+    tr.load_trainer_state(state)
+    assert tr._warmup_left == tr.graph_warmup == 2  # this object's eager steps, not the checkpoint's counter
+    assert tr.step_count == 1234
+    assert tr._graphs is None and tr._static is None and tr._fopt is None
+    logs, td = tr.step(batch, w, k=1, flip=True)
+    assert np.isfinite(logs).all() and td.shape == (batch[0].shape[0],)
+    assert tr.step_count == 1235 and tr._warmup_left == 1
+    ost = tr.opt.state_dict()["state"]
+    assert all(float(ost[i]["step"]) == float(s["step"]) + 1 for i, s in state["optimizer_state_dict"]["state"].items())
+
+
 def test_trainer_state_loader_rejects_other_globals():
     import pickle
 

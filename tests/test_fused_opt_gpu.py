@@ -2,7 +2,8 @@
 torch.optim.Adam (L2 weight decay) + GradScaler.update + the soft target update of utils.py:28-31 + zero_grad, in
 three launches over the flat gradient bucket (workers.py:565-583).  Against PyTorch's own path (FUSED_OPT = False):
 the same steps within float32 rounding of the gradient norm and the Adam moments; a non-finite gradient skips Adam
-exactly as GradScaler.step does; the optimiser state keeps the reference's state_dict format and resumes exactly."""
+exactly as GradScaler.step does; the optimiser state keeps the reference's state_dict format and resumes exactly,
+also into a trainer that captures its step: after eager steps of its own, with its state built outside the capture."""
 import numpy as np
 import pytest
 import torch
@@ -128,16 +129,16 @@ def test_non_finite_gradient_skips_adam_but_not_the_target_update(T):
     tr.step(bs[0], w, k=0, flip=False)
     tr.step(bs[0], w, k=2, flip=False)
     torch.cuda.synchronize()
-    assert tr._fopt is not None and float(tr._fopt["step"]) == 2.0
+    assert tr._fopt is not None and float(tr._fopt.steps) == 2.0
     p_before, t_before = _flat(tr.model).clone(), _flat(tr.target).clone()
-    step_before, scale_before = float(tr._fopt["step"]), float(tr.scaler.get_scale())
-    m_before = tr._fopt["m"].clone()
+    step_before, scale_before = float(tr._fopt.steps), float(tr.scaler.get_scale())
+    m_before = tr._fopt.m.clone()
     tr.flat_grad.fill_(1.0)
     tr.flat_grad[123] = float("inf")
     tr._update()
     torch.cuda.synchronize()
     assert torch.equal(_flat(tr.model), p_before)  # Adam skipped
-    assert torch.equal(tr._fopt["m"], m_before) and float(tr._fopt["step"]) == step_before
+    assert torch.equal(tr._fopt.m, m_before) and float(tr._fopt.steps) == step_before
     assert float(tr.scaler.get_scale()) == scale_before * 0.5  # GradScaler backoff
     tau = cfg.TARGET_MODEL_TAU
     want = t_before * (1.0 - tau) + p_before * tau  # the soft update still ran
@@ -146,7 +147,7 @@ def test_non_finite_gradient_skips_adam_but_not_the_target_update(T):
     # and a finite step afterwards advances the step counter again
     tr.step(bs[0], w, k=1, flip=True)
     torch.cuda.synchronize()
-    assert float(tr._fopt["step"]) == step_before + 1
+    assert float(tr._fopt.steps) == step_before + 1
 
 
 def test_fused_step_advances_the_packed_weight_caches(T):
@@ -198,4 +199,67 @@ def test_fused_optimiser_state_resumes_exactly(T, monkeypatch):
     torch.cuda.synchronize()
     assert la == lb
     assert torch.equal(_flat(a.model), _flat(b.model))
-    assert torch.equal(a._fopt["m"], b._fopt["m"]) and torch.equal(a._fopt["v"], b._fopt["v"])
+    assert torch.equal(a._fopt.m, b._fopt.m) and torch.equal(a._fopt.v, b._fopt.v)
+
+
+def _resume(T, cfg, src, state, **kw):
+    """A fresh trainer resumed from ``state``, with what a checkpoint does not carry aligned to ``src``: the target
+    network (the reference restarts it from the model) and the GradScaler."""
+    tr = T.Trainer(cfg, device="cuda", **kw)
+    tr.load_trainer_state(state)
+    tr.target.load_state_dict(src.target.state_dict())
+    tr.scaler.load_state_dict(src.scaler.state_dict())
+    return tr
+
+
+def test_resumed_graph_trainer_captures_after_its_own_warmup(T, monkeypatch):
+    """A graph trainer resumed from a checkpoint takes its own graph_warmup eager steps (the checkpoint's step_count
+    says nothing about this object), builds the fused optimiser's state and the GradScaler's tensors outside the
+    capture, and its replays advance the Adam step and moments instead of resetting them to the checkpoint's."""
+    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
+    cfg = _cfg(T)
+    bs = _batches(T, cfg, 2)
+    w = torch.rand(32, device="cuda") + 0.5
+    torch.manual_seed(4)
+    a = T.Trainer(cfg, device="cuda", graph=True, graph_warmup=2)
+    a.scaler = torch.amp.GradScaler("cuda", init_scale=1.0 / 16)
+    for i in range(3):
+        a.step(bs[i % 2], w, k=i, flip=False)
+    torch.cuda.synchronize()
+    assert a._graphs is not None
+    b = _resume(T, cfg, a, a.trainer_state(), graph=True, graph_warmup=2)
+    scale0, tracker0 = float(a.scaler.get_scale()), int(a.scaler.state_dict()["_growth_tracker"])
+    assert b.step_count == 3
+    seen = []
+    for i in range(4):
+        b.step(bs[i % 2], w, k=i, flip=bool(i % 2))
+        torch.cuda.synchronize()
+        assert (b._graphs is not None) == (i >= 2), i  # two eager steps of its own, then the capture
+        assert b._fopt is not None
+        assert float(b.flat_grad.abs().max()) == 0.0, i
+        seen.append(([float(b.opt.state[p]["step"]) for p in b.params], b._fopt.m.clone(), b._fopt.v.clone()))
+    (steps3, m3, v3), (steps4, m4, v4) = seen[2], seen[3]
+    assert all(s == 6.0 for s in steps3) and all(s == 7.0 for s in steps4)  # replays advance it: 3 + 4
+    assert not torch.equal(m3, m4) and not torch.equal(v3, v4)
+    assert float(b.scaler.get_scale()) == scale0
+    assert int(b.scaler._growth_tracker) == tracker0 + 4
+
+
+@pytest.mark.parametrize("amp", [False, True])
+def test_resumed_graph_trainer_follows_resumed_eager_trainer(T, amp):
+    """From one checkpoint, the resumed graph trainer (two eager steps of its own, then captured) follows the resumed
+    eager trainer within tests/test_trainer.py's graph-follows-eager bound at the same shape and step count."""
+    from test_trainer import _assert_graph_follows_eager, _graph_vs_eager_setup, _graph_vs_eager_state
+    cfg, batch, w = _graph_vs_eager_setup(T)
+    torch.manual_seed(0)
+    src = T.Trainer(cfg, device="cuda", graph=False, amp=amp)
+    for i in range(3):
+        src.step(batch, w, k=i % 4, flip=bool(i % 2))
+    state = src.trainer_state()
+    runs = []
+    for kw in (dict(graph=False), dict(graph=True, graph_warmup=2)):
+        tr = _resume(T, cfg, src, state, amp=amp, **kw)
+        logs = [tr.step(batch, w, k=i % 4, flip=bool(i % 2))[0] for i in range(4)]
+        assert (tr._graphs is not None) == tr.graph
+        runs.append(_graph_vs_eager_state(tr, logs))
+    _assert_graph_follows_eager(runs[0], runs[1], amp)
