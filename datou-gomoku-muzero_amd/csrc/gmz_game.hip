@@ -284,6 +284,304 @@ GMZ_EXPORT int gmz_game_anchor_move(const int8_t *boards, const int8_t *players,
   return 0;
 }
 
+namespace gmz {
+
+constexpr int VCF_MAX_DEPTH = 16, VCF_MAX_NODES = 1 << 20;
+constexpr int VCF_MULTI = 0x4000;  // info bit: T(c) holds two or more cells (a cell index is below 512)
+
+constexpr int VCF_LINES = 2 * 22 - 1;  // lines of one orientation on the largest board: its 43 diagonals
+
+__device__ __forceinline__ uint64_t vcf_uniform(uint64_t x) {  // a wave-uniform 64-bit value, in scalar registers
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+}
+
+// Cells j * 64 .. j * 64 + 63 of a cell mask kept as 32-bit words in LDS, wave-uniform.
+__device__ __forceinline__ uint64_t vcf_word(const uint32_t *mask, int j) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)mask[2 * j + 1]) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)mask[2 * j]);
+}
+
+// The line of orientation d (0: (0,1), 1: (1,0), 2: (1,1), 3: (1,-1)) through cell (r, c) and the cell's bit in it.
+// A step along the direction raises the bit index by one: the index is the column in a row and the row elsewhere.
+__device__ __forceinline__ void vcf_line(int d, int r, int c, int size, int &line, int &pos) {
+  line = d == 0 ? r : d == 1 ? c : d == 2 ? r - c + size - 1 : r + c;
+  pos = d == 0 ? c : r;
+}
+
+__device__ __forceinline__ bool vcf_empty(const uint32_t (*lines)[4][VCF_LINES], int r, int c) {
+  return !(((lines[0][0][r] | lines[1][0][r]) >> c) & 1);
+}
+
+// What the empty cell (r0, c0) is in one node of the forced-win search.  The board is kept as bit
+// lines: lines[s][d][l] holds the stones of the attacker (s = 0) or the defender (s = 1) on line l of orientation d.
+// Per direction the cells of the line at most n-1 steps from the cell, as far as the board goes (back against the
+// direction, fwd along it), are a shifted piece of two line words (bit k + back = the cell k steps along), and every
+// window of n cells that holds the cell is a run of n bits in it.  five_p / five_o: a window with n-1 stones of the
+// attacker / of the defender (the cell is its one other cell); four: a window with n-2 attacker stones, no defender
+// stone and so one more empty cell e; e1 the first such e, multi: another window gave a different e.
+__device__ __forceinline__ void vcf_cell(const uint32_t (*lines)[4][VCF_LINES], int size, int n, int r0, int c0,
+                                         bool &five_p, bool &five_o, bool &four, bool &multi, int &e1) {
+  const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+  const uint32_t run = (1u << n) - 1;
+  const int cell = r0 * size + c0;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    int back = n - 1, fwd = n - 1;
+    if (dr[d]) {
+      back = min(back, r0);
+      fwd = min(fwd, size - 1 - r0);
+    }
+    if (dc[d] > 0) {
+      back = min(back, c0);
+      fwd = min(fwd, size - 1 - c0);
+    } else if (dc[d] < 0) {
+      back = min(back, size - 1 - c0);
+      fwd = min(fwd, c0);
+    }
+    if (back + fwd < n - 1) continue;  // no window through the cell lies on the board
+    int line, pos;
+    vcf_line(d, r0, c0, size, line, pos);
+    const uint32_t span = (2u << (back + fwd)) - 1;  // back + fwd + 1 <= size bits
+    const uint32_t own = (lines[0][d][line] >> (pos - back)) & span, opp = (lines[1][d][line] >> (pos - back)) & span;
+    if (__popc(own) < n - 2 && __popc(opp) < n - 1) continue;
+    const int step = dr[d] * size + dc[d];
+    for (int w = 0; w <= back + fwd - (n - 1); ++w) {  // the window of bits [w, w + n)
+      const uint32_t wm = run << w;
+      const int n_own = __popc(own & wm), n_opp = __popc(opp & wm);
+      five_p |= n_own == n - 1;
+      five_o |= n_opp == n - 1;
+      if (n_own == n - 2 && n_opp == 0) {
+        const int e = cell + (__builtin_ctz(wm & ~own & ~(1u << back)) - back) * step;
+        if (!four) e1 = e;
+        else if (e != e1) multi = true;
+        four = true;
+      }
+    }
+  }
+}
+
+// The exact, depth-limited forced-win (VCF) search of DESIGN.md §8b for G boards: one wave per board, a workgroup of
+// one wave, so a board at its node budget holds nothing but its own wave.  The search is serial and wave-uniform
+// (every branch is taken on a ballot or on a value all lanes read from LDS); a node's work is wide: lane l classifies
+// the cells l, l + 64, ... (up to 8), and a ballot per group of 64 cells gives the five and four masks in ascending
+// cell order.  Below the root a node differs from the one above it by two stones, so it takes that node's masks and
+// replies and classifies again only the cells within n-1 steps of a stone along a line (16 (n-1) cells: one per lane
+// at n = 5).  The board (as bit lines in the four orientations, so that a cell reads two words per direction), per
+// level the three masks, the candidates left, each four's reply (info) and the two stones played are in LDS; nothing
+// is kept in global memory, and the only atomics are LDS ORs and ANDs on the bit lines and masks.
+__global__ void __launch_bounds__(WAVE) k_vcf(const int8_t *__restrict__ boards, const int8_t *__restrict__ players,
+                                              const int32_t *__restrict__ game, int size, int n, int max_depth,
+                                              int max_nodes, int8_t *__restrict__ status, int32_t *__restrict__ moves,
+                                              int32_t *__restrict__ lengths, int32_t *__restrict__ nodes,
+                                              int32_t *__restrict__ actions) {
+  __shared__ uint32_t lines[2][4][VCF_LINES];
+  __shared__ uint16_t rc[MAX_A];                  // a cell's row << 8 | column
+  __shared__ int16_t info[VCF_MAX_DEPTH][MAX_A];  // of a four cell c: T(c)'s first cell, | VCF_MULTI
+  __shared__ uint32_t masks[VCF_MAX_DEPTH][3][2 * NJ];  // per level five(b, p), five(b, -p), fours(b, p): bit = cell
+  __shared__ uint64_t cand[VCF_MAX_DEPTH][NJ];    // the level's candidates not yet tried
+  __shared__ int16_t played[VCF_MAX_DEPTH][2];    // the attacker's four and the defender's reply on the board
+  const int g = blockIdx.x, A = size * size, lane = threadIdx.x;
+  if (game && game[g] < 0) {  // an idle arena slot: actions[g] stays as it is
+    if (lane == 0) {
+      status[g] = 3;
+      moves[g] = -1;
+      if (lengths) lengths[g] = 0;
+      if (nodes) nodes[g] = 0;
+    }
+    return;
+  }
+  for (int i = lane; i < 2 * 4 * VCF_LINES; i += WAVE) (&lines[0][0][0])[i] = 0;
+  __syncthreads();
+  const int p = players[g];
+  const int8_t *src = boards + (size_t)g * A;
+  for (int i = lane; i < A; i += WAVE) {
+    const int r = i / size, c = i - r * size, v = src[i];
+    rc[i] = (uint16_t)(r << 8 | c);
+    if (v != 0)
+      for (int d = 0; d < 4; ++d) {
+        int line, pos;
+        vcf_line(d, r, c, size, line, pos);
+        atomicOr(&lines[v == p ? 0 : 1][d][line], 1u << pos);
+      }
+  }
+  __syncthreads();
+  // a stone of side s goes on or off the cell: lane s * 4 + d flips its bit in orientation d (eight distinct words)
+  auto flip = [&](int c0, int c1) {
+    if (lane < 8) {
+      const int s = lane >> 2, d = lane & 3, x = rc[s ? c1 : c0];
+      int line, pos;
+      vcf_line(d, x >> 8, x & 255, size, line, pos);
+      lines[s][d][line] ^= 1u << pos;
+    }
+  };
+  const int nj = (A + WAVE - 1) / WAVE;
+  int level = 0, count = 0, st = 0, mv = -1, len = 0;
+  for (;;) {  // solve() of the node at ``level``, with max_depth - level attacker moves left
+    if (++count > max_nodes) {
+      st = 2;
+      break;
+    }
+    const bool leaf = max_depth - level <= 1;
+    if (level == 0) {  // the root: every cell
+#pragma unroll 1
+      for (int j = 0; j < nj; ++j) {
+        const int cell = j * WAVE + lane;
+        bool five_p = false, five_o = false, four = false, multi = false;
+        int e1 = 0;
+        if (cell < A) {
+          const int r0 = rc[cell] >> 8, c0 = rc[cell] & 255;
+          if (vcf_empty(lines, r0, c0)) vcf_cell(lines, size, n, r0, c0, five_p, five_o, four, multi, e1);
+        }
+        const uint64_t wp = __ballot(five_p), wo = __ballot(five_o), wf = __ballot(four);
+        if (four) info[0][cell] = (int16_t)(e1 | (multi ? VCF_MULTI : 0));
+        if (lane < 2) {  // lane 0 the low words, lane 1 the high ones
+          masks[0][0][2 * j + lane] = (uint32_t)(wp >> (32 * lane));
+          masks[0][1][2 * j + lane] = (uint32_t)(wo >> (32 * lane));
+          masks[0][2][2 * j + lane] = (uint32_t)(wf >> (32 * lane));
+        }
+      }
+    } else {
+      // below the root: the level above's masks and replies, with the cells put right that share a window with one
+      // of the two stones just played (at most n-1 steps from it along a line), and the two cells themselves
+      for (int i = lane; i < 3 * 2 * NJ; i += WAVE) (&masks[level][0][0])[i] = (&masks[level - 1][0][0])[i];
+      for (int i = lane; i < A; i += WAVE) info[level][i] = info[level - 1][i];
+      __syncthreads();
+      const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+      const int m = 2 * (n - 1);
+      for (int idx = lane; idx < 8 * m + 2; idx += WAVE) {
+        const bool self = idx >= 8 * m;
+        int r, c;
+        if (self) {
+          const int x = rc[played[level - 1][idx - 8 * m]];
+          r = x >> 8;
+          c = x & 255;
+        } else {
+          const int s = idx / (4 * m), rem = idx - s * 4 * m, d = rem / m, kk = rem - d * m;
+          const int k = kk - (n - 1) + (kk >= n - 1 ? 1 : 0);  // -(n-1) .. -1, 1 .. n-1
+          const int x = rc[played[level - 1][s]];
+          r = (x >> 8) + k * dr[d];
+          c = (x & 255) + k * dc[d];
+        }
+        if (r < 0 || r >= size || c < 0 || c >= size) continue;
+        const int cell = r * size + c;
+        bool five_p = false, five_o = false, four = false, multi = false;
+        int e1 = 0;
+        if (!self && vcf_empty(lines, r, c)) vcf_cell(lines, size, n, r, c, five_p, five_o, four, multi, e1);
+        // lanes that meet on a cell write the same; lanes on other cells of a word go through the LDS atomics
+        const uint32_t bit = 1u << (cell & 31);
+        uint32_t *w = &masks[level][0][cell >> 5];  // the same word of the next two masks: + 2 NJ, + 4 NJ
+        five_p ? atomicOr(w, bit) : atomicAnd(w, ~bit);
+        five_o ? atomicOr(w + 2 * NJ, bit) : atomicAnd(w + 2 * NJ, ~bit);
+        four ? atomicOr(w + 4 * NJ, bit) : atomicAnd(w + 4 * NJ, ~bit);
+        if (four) info[level][cell] = (int16_t)(e1 | (multi ? VCF_MULTI : 0));
+      }
+    }
+    __syncthreads();
+    int first_five = -1, fo_cell = -1, fo_count = 0;
+    for (int j = 0; j < nj; ++j) {
+      const uint64_t wp = vcf_word(masks[level][0], j), wo = vcf_word(masks[level][1], j);
+      if (wp && first_five < 0) first_five = j * WAVE + __builtin_ctzll(wp);
+      if (wo) {
+        if (fo_count == 0) fo_cell = j * WAVE + __builtin_ctzll(wo);
+        fo_count += __popcll(wo);
+      }
+    }
+    if (first_five >= 0) {  // 2. the attacker completes a five
+      st = 1;
+      len = level + 1;
+      mv = level ? played[0][0] : first_five;
+      break;
+    }
+    // 3.-5. the candidates: none, the fours, or the one four that blocks
+    if (lane == 0)
+      for (int j = 0; j < nj; ++j) {
+        uint64_t w = leaf || fo_count >= 2 ? 0 : (uint64_t)masks[level][2][2 * j + 1] << 32 | masks[level][2][2 * j];
+        if (fo_count == 1) w = j == fo_cell / WAVE ? w & (1ull << (fo_cell % WAVE)) : 0;
+        cand[level][j] = w;
+      }
+    __syncthreads();
+    bool done = false;
+    for (;;) {  // 6. the next candidate of this level, or back to the level above
+      int c = -1;
+      for (int j = 0; j < nj; ++j) {
+        const uint64_t w = vcf_uniform(cand[level][j]);
+        if (w) {
+          c = j * WAVE + __builtin_ctzll(w);
+          if (lane == 0) cand[level][j] = w & (w - 1);
+          break;
+        }
+      }
+      if (c < 0) {  // 7. no candidate won
+        if (level == 0) {
+          done = true;
+          break;
+        }
+        --level;
+        flip(played[level][0], played[level][1]);
+        __syncthreads();
+        continue;
+      }
+      const int inf = __builtin_amdgcn_readfirstlane((int)info[level][c]), e = inf & (MAX_A - 1);
+      if (inf & VCF_MULTI) {  // a double four
+        st = 1;
+        len = level + 2;
+        mv = level ? played[0][0] : c;
+        done = true;
+        break;
+      }
+      flip(c, e);
+      if (lane == 0) {
+        played[level][0] = (int16_t)c;
+        played[level][1] = (int16_t)e;
+      }
+      ++level;
+      __syncthreads();
+      break;
+    }
+    if (done) break;
+  }
+  if (lane == 0) {
+    status[g] = (int8_t)st;
+    moves[g] = mv;
+    if (lengths) lengths[g] = len;
+    if (nodes) nodes[g] = count;
+    if (actions && st == 1) actions[g] = mv;
+  }
+}
+
+}  // namespace gmz
+
+GMZ_EXPORT int gmz_game_vcf(const int8_t *boards, const int8_t *players, const int32_t *game, int G, int size,
+                            int n_in_row, int max_depth, int max_nodes, int8_t *status, size_t status_bytes,
+                            int32_t *moves, size_t moves_bytes, int32_t *lengths, size_t lengths_bytes, int32_t *nodes,
+                            size_t nodes_bytes, int32_t *actions, size_t actions_bytes, void *stream) {
+  if (G <= 0) return fail("gmz_game_vcf: bad shape: G must be >= 1");
+  if (size <= 0 || size * size > MAX_A)
+    return fail("gmz_game_vcf: bad shape: size must be >= 1 and size * size <= 512");
+  if (n_in_row < 3 || n_in_row > size) return fail("gmz_game_vcf: n_in_row must be in [3, size]");
+  if (max_depth < 1 || max_depth > VCF_MAX_DEPTH) return fail("gmz_game_vcf: max_depth must be in [1, 16]");
+  if (max_nodes < 1 || max_nodes > VCF_MAX_NODES) return fail("gmz_game_vcf: max_nodes must be in [1, 1048576]");
+  if (!boards || !players || !status || !moves)
+    return fail(std::string("gmz_game_vcf: null ") +
+                (!boards ? "boards" : !players ? "players" : !status ? "status" : "moves"));
+  const struct {
+    const char *name;
+    const void *p;
+    size_t have, each;
+  } bufs[5] = {{"status", status, status_bytes, 1}, {"moves", moves, moves_bytes, 4},
+               {"lengths", lengths, lengths_bytes, 4}, {"nodes", nodes, nodes_bytes, 4},
+               {"actions", actions, actions_bytes, 4}};
+  for (const auto &x : bufs)
+    if (x.p && x.have < (size_t)G * x.each)
+      return fail(std::string("gmz_game_vcf: ") + x.name + " holds " + std::to_string(x.have) + " bytes, G * " +
+                  std::to_string(x.each) + " = " + std::to_string((size_t)G * x.each));
+  hipLaunchKernelGGL(k_vcf, dim3(G), dim3(WAVE), 0, (hipStream_t)stream, boards, players, game, size, n_in_row,
+                     max_depth, max_nodes, status, moves, lengths, nodes, actions);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
 GMZ_EXPORT int gmz_game_check_win(const int8_t *boards, int G, int size, int n_in_row, const int32_t *moves,
                                   uint8_t *out, void *stream) {
   if (G <= 0 || size <= 0 || size * size > MAX_A) return fail("gmz_game_check_win: bad shape");

@@ -144,7 +144,8 @@ class BatchedSelfPlayEngine:
         self._bud_flip = 0
         self._refill = None  # play_refill's slot arrays and pinned read-back buffers (arena)
         self._refill_pending = False
-        self._state_ptrs = None  # device pointers of the engine-owned game state (anchor_move)
+        self._state_ptrs = None  # device pointers of the engine-owned game state (anchor_move, vcf_move)
+        self.vcf_status = self.vcf_moves = None  # the last vcf_move launch's statuses and moves (made at the first)
         self.finished_seen = 0  # the match's finished-games counter as of the last status read (play_refill)
         self.moves_played = 0   # moves counted from the statuses read after play_refill calls
         self._hb_net = None     # the backend whose pool the last placement was checked against
@@ -576,6 +577,26 @@ class BatchedSelfPlayEngine:
             self._stream(stream)))
         return self.action
 
+    def vcf_move(self, depth=None, nodes=None, stream=None):
+        """The forced-win solver (gmz_game_vcf, see ``vcf``) for the side to move on the engine's own device boards,
+        in one launch on ``stream`` with no host wait: where it finds a win its move replaces the entry of
+        ``self.action`` (after anchor_move: the threat rule's move), every other entry stays.  Returns
+        ``self.action``; the statuses and moves of the launch stay in ``self.vcf_status`` / ``self.vcf_moves``."""
+        if self._state_ptrs is None:
+            p = [ctypes.c_void_p() for _ in range(4)]
+            check(self.lib.gmz_engine_game_state(self.handle, *[ctypes.byref(x) for x in p]))
+            self._state_ptrs = p
+        if self.vcf_status is None:
+            self.vcf_status = torch.zeros(self.G, dtype=torch.int8, device=self.device)
+            self.vcf_moves = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
+        game = self._refill["game"] if self._refill is not None else None
+        check(self.lib.gmz_game_vcf(
+            self._state_ptrs[0], self._state_ptrs[1], ptr(game), self.G, self.size, self.cfg.N_IN_ROW,
+            VCF_DEPTH if depth is None else int(depth), VCF_NODES if nodes is None else int(nodes),
+            ptr(self.vcf_status), _lib.nbytes(self.vcf_status), ptr(self.vcf_moves), _lib.nbytes(self.vcf_moves),
+            None, 0, None, 0, ptr(self.action), _lib.nbytes(self.action), self._stream(stream)))
+        return self.action
+
     def winning_scan(self, boards, players, action=None, counters=None, stream=None):
         """workers.py:49-123 find_winning_moves_rebuilt on the device for G positions (see
         ``winning_scan``); ``counters`` = (missed_fives, missed_totals) int32[G] accumulated in place."""
@@ -940,6 +961,38 @@ def anchor_move(boards, players, noise=None, kind="threat", scale=0.0, n_in_row=
                                  anchor_kind(kind), float(scale), ptr(act), _lib.nbytes(act), ptr(sc), _lib.nbytes(sc),
                                  _lib.stream_ptr(stream)))
     return (act, sc) if scores else act
+
+
+VCF_DEPTH, VCF_NODES = 10, 2048  # the solver's defaults
+
+
+def vcf(boards, players, depth=VCF_DEPTH, nodes=VCF_NODES, game=None, actions=None, stream=None, n_in_row=5):
+    """The forced-win (VCF) solver on G boards (``gmz_game_vcf``; the rule: DESIGN.md §8b): an exact depth-first
+    search, at most ``depth`` attacker moves deep and ``nodes`` nodes per board, for a win of the player to move by
+    fours that each force the reply, in one launch.
+
+    boards int8[G,S,S] and players int8[G] on the device.  ``game`` int32[G]: a negative entry skips that board.
+    ``actions`` int32[G] on the device is updated in place: entry g becomes the solver's move where it found a win
+    and stays as it is everywhere else.  Returns (status int8[G]: 0 none, 1 found, 2 node budget used up, 3 skipped;
+    move int32[G], -1 unless status is 1; length int32[G], the attacker moves of the line; nodes int32[G])."""
+    L = _lib.load()
+    b = torch.as_tensor(boards).contiguous()
+    if b.dtype != torch.int8 or b.dim() < 2:
+        raise ValueError("vcf: boards must be int8 [G, S, S]")
+    G, S = b.shape[0], b.shape[-1]
+    p = torch.as_tensor(players, dtype=torch.int8).to(b.device).contiguous()
+    gm = None if game is None else torch.as_tensor(game, dtype=torch.int32).to(b.device).contiguous()
+    if b.numel() != G * S * S or p.numel() != G or (gm is not None and gm.numel() != G):
+        raise ValueError("vcf: expected boards [G, S, S] with players (and game) of G entries")
+    if actions is not None and (not torch.is_tensor(actions) or actions.dtype != torch.int32
+                                or actions.device != b.device or not actions.is_contiguous()):
+        raise ValueError("vcf: actions must be a contiguous int32 tensor on the boards' device (updated in place)")
+    st = torch.empty(G, dtype=torch.int8, device=b.device)
+    mv, ln, nd = (torch.empty(G, dtype=torch.int32, device=b.device) for _ in range(3))
+    check(L.gmz_game_vcf(ptr(b), ptr(p), ptr(gm), G, S, int(n_in_row), int(depth), int(nodes), ptr(st), _lib.nbytes(st),
+                         ptr(mv), _lib.nbytes(mv), ptr(ln), _lib.nbytes(ln), ptr(nd), _lib.nbytes(nd), ptr(actions),
+                         _lib.nbytes(actions), _lib.stream_ptr(stream)))
+    return st, mv, ln, nd
 
 
 def _has_five(board, n_in_row=5):

@@ -273,6 +273,29 @@ int gmz_game_anchor_move(const int8_t *boards_dev, const int8_t *players_dev, co
                          double scale, int32_t *actions_dev, size_t actions_bytes, int64_t *scores_dev,
                          size_t scores_bytes, void *stream);
 
+/* An exact, depth-limited search for a forced win by continuous fours (VCF) of the player to move (p =
+ * players_dev[g]) on G boards, in one launch (additive, ABI stays 10; the rule in full: DESIGN.md §8b).  A window is
+ * n_in_row cells in a line, wholly on the board.  five(b, s): the empty cells that complete a window of s (overlines
+ * included); fours(b, s): the empty cells c with a window of n_in_row - 2 stones of s, c and one more empty cell e;
+ * T(c) the set of such e.  solve(b, d): count the node, and stop everything with status 2 once the count exceeds
+ * max_nodes; a cell in five(b, p) wins (the smallest, length 1); d <= 1 fails; two or more cells in five(b, -p) fail;
+ * the cells of fours(b, p) in ascending order (with one cell in five(b, -p): that cell alone, if it is a four): two or
+ * more cells in T(c) win (length 2), otherwise p plays c, -p the one cell of T(c), and solve(b', d - 1) decides, a win
+ * there being a win here with move c and one more move.  Depth-first in that order, no iterative deepening.
+ * status_dev int8[G]: 0 no forced win within max_depth attacker moves, 1 found, 2 node budget used up, 3 board skipped
+ * (game_dev[g] < 0; game_dev int32[G] or NULL: gmz_engine_play_refill's slot_game_dev).  moves_dev int32[G]: the first
+ * move of the line found, -1 unless status is 1.  lengths_dev (nullable) int32[G]: the line's attacker moves, 0 unless
+ * status is 1.  nodes_dev (nullable) int32[G]: the calls of solve (max_nodes + 1 with status 2, 0 with status 3).
+ * actions_dev (nullable, in/out) int32[G]: entry g is overwritten with the move where status is 1 and left alone
+ * everywhere else.  Refused before any launch, with nothing written: G < 1, size < 1 or size^2 > 512, n_in_row
+ * outside [3, size], max_depth outside [1, 16], max_nodes outside [1, 1 << 20], null boards, players, status or moves,
+ * status_bytes < G, moves_bytes / lengths_bytes / nodes_bytes / actions_bytes < G * 4 (the last three only with their
+ * pointer).  Stream-ordered; never synchronises. */
+int gmz_game_vcf(const int8_t *boards_dev, const int8_t *players_dev, const int32_t *game_dev, int G, int size,
+                 int n_in_row, int max_depth, int max_nodes, int8_t *status_dev, size_t status_bytes,
+                 int32_t *moves_dev, size_t moves_bytes, int32_t *lengths_dev, size_t lengths_bytes, int32_t *nodes_dev,
+                 size_t nodes_bytes, int32_t *actions_dev, size_t actions_bytes, void *stream);
+
 /* ------------------------------------------------------------------ HashNet test network */
 /* Deterministic integer-hash network (definition: oracle/hashnet.py) used for tree parity.
  * Hidden state = uint32 id per slot in hid_pool_dev[G*slots].

@@ -1,0 +1,356 @@
+"""The forced-win (VCF) solver on the GPU (gmz_game_vcf, engine.vcf, arena.AnchorPlayer("vcf")).  Every comparison is
+exact: status, move, length and node count are integers that the kernel and the numpy model (tests/vcf_ref.py) must
+give alike, since both walk the same tree in the same order.
+
+  1. kernel against model on every position of model games between two threat anchors (noise scale 3e3, from the
+     empty board), 6x6 to 22x22, n = 4 and 5, 1 / 65 / about 1,000 boards, in guarded buffers;
+  2. the limits: max_depth 1, 2, 16 and max_nodes 1, 8, 64 on the 9x9 set;
+  3. the hand-built positions of tests/test_vcf.py;
+  4. game_dev with negative entries, actions_dev in/out, the nullable outputs;
+  5. engine.vcf;
+  6. an arena match anchor:vcf against anchor:threat equals the model's games, one and two streams;
+  7. anchor:vcf against a HashNet side equals the same games played one at a time;  8. the command line."""
+import functools
+import json
+
+import numpy as np
+import pytest
+
+import anchor_ref as R
+import test_vcf as TV
+import vcf_ref as V
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+DEPTH, NODES = 10, 4096  # the default case's limits (the entry point's own default budget is 2,048 nodes)
+# (size, n): (model games, seed) of the position pool.  The seeds are chosen so that the model's own results meet the
+# conditions asserted in test 1 (seed 1 does everywhere).
+POOLS = {(6, 4): (75, 1), (6, 5): (34, 1), (9, 5): (32, 1), (15, 5): (26, 1), (19, 5): (8, 1), (22, 5): (8, 1)}
+ALL = 0  # a batch of the whole pool
+
+
+@pytest.fixture(scope="module")
+def mods():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import datou_gomoku_muzero_amd._lib as L
+    import datou_gomoku_muzero_amd.arena as AR
+    import datou_gomoku_muzero_amd.engine as E
+    from datou_gomoku_muzero_amd.config import GmzConfig
+    return dict(L=L, AR=AR, E=E, Cfg=GmzConfig, lib=L.load())
+
+
+@functools.lru_cache(maxsize=None)
+def pool(S, n):
+    """(boards int8 [P, A], players int8 [P]) of the model games, read-only."""
+    games, seed = POOLS[(S, n)]
+    b, p = V.threat_game_positions(S, n, games, seed)
+    b.setflags(write=False)
+    p.setflags(write=False)
+    return b, p
+
+
+@functools.lru_cache(maxsize=None)
+def reference(S, n, depth=DEPTH, nodes=NODES):
+    """The model's (status, move, length, nodes) on the whole pool: computed once, shared, read-only."""
+    b, p = pool(S, n)
+    out = V.solve_batch(b, p, n, depth, nodes)
+    for o in out:
+        o.setflags(write=False)
+    return out
+
+
+def subset(S, n, G):
+    """Indices of a batch of G positions of the pool: the whole pool for ALL; one position with a win of length >= 3
+    for G = 1; otherwise up to G / 2 such wins and evenly spaced positions for the rest."""
+    st, _, ln, _ = reference(S, n)
+    P = st.size
+    if G == ALL:
+        return np.arange(P)
+    deep = np.flatnonzero((st == V.FOUND) & (ln >= 3))
+    if G == 1:
+        return deep[:1]
+    pick = [int(i) for i in deep[:G // 2]]
+    pick += [int(i) for i in np.linspace(0, P - 1, G).astype(int) if i not in pick][:G - len(pick)]
+    pick += [i for i in range(P) if i not in pick][:G - len(pick)]
+    return np.array(sorted(pick))
+
+
+def run_kernel(m, boards, players, n, depth, nodes, game=None, actions=None, outputs=True):
+    """gmz_game_vcf into guarded buffers: dict(status, move, length, nodes, actions) as numpy (None where not asked
+    for).  ``actions``: int32 [G] going in."""
+    from kernel_guards import Buf
+    L, lib = m["L"], m["lib"]
+    G = boards.shape[0]
+    S = int(round(boards[0].size ** 0.5))
+    b = torch.from_numpy(np.array(boards, np.int8)).cuda()  # copies: the pools are read-only
+    p = torch.from_numpy(np.array(players, np.int8)).cuda()
+    gm = None if game is None else torch.from_numpy(np.ascontiguousarray(game, dtype=np.int32)).cuda()
+    st = Buf(G, torch.int8, off=1, fill=-7)
+    mv = Buf(G, torch.int32, off=1, fill=-7)
+    ln = Buf(G, torch.int32, off=1, fill=-7) if outputs else None
+    nd = Buf(G, torch.int32, off=1, fill=-7) if outputs else None
+    ac = None if actions is None else Buf(G, torch.int32, off=1, fill=-7, data=actions)
+
+    def pb(x):
+        return (L.ptr(x.t), L.nbytes(x.t)) if x is not None else (None, 0)
+    L.check(lib.gmz_game_vcf(L.ptr(b), L.ptr(p), L.ptr(gm), G, S, n, depth, nodes, *pb(st), *pb(mv), *pb(ln), *pb(nd),
+                             *pb(ac), L.stream_ptr()))
+    torch.cuda.synchronize()
+    bufs = dict(status=st, move=mv, length=ln, nodes=nd, actions=ac)
+    assert all(x.intact() for x in bufs.values() if x is not None)
+    return {k: (None if x is None else x.t.cpu().numpy()) for k, x in bufs.items()}
+
+
+def assert_equal(got, want, what):
+    for k, w in zip(("status", "move", "length", "nodes"), want):
+        assert np.array_equal(got[k], w), (what, k, np.flatnonzero(got[k] != w)[:8])
+
+
+# ---------------------------------------------------------------------------------------------- 1. kernel against model
+CASES = [(6, 4, 1), (6, 4, 65), (6, 4, ALL), (6, 5, 1), (6, 5, 65), (6, 5, ALL), (9, 5, 1), (9, 5, 65), (9, 5, ALL),
+         (15, 5, ALL), (19, 5, 65), (22, 5, 65)]
+
+
+@pytest.mark.parametrize("S,n,G", CASES, ids=["%dx%d-n%d-G%s" % (c[0], c[0], c[1], c[2] or "all") for c in CASES])
+def test_kernel_equals_the_model(mods, S, n, G):
+    """Conditions on the model's own results, so that the batch cannot be trivial.  On a whole pool (about 1,000
+    positions): at least 30 wins of length >= 3, 5 of them of length >= 6, at most 5 % at the node budget — but on 6x6
+    with n = 5, where a line has two windows only and long lines of fours hardly exist: 5 wins of length >= 3.  A
+    batch of 65: 3 wins of length >= 3; a batch of 1: that position is one."""
+    idx = subset(S, n, G)
+    b, p = pool(S, n)
+    want = [w[idx] for w in reference(S, n)]
+    st, _, ln, nd = want
+    deep, deeper = int(((st == V.FOUND) & (ln >= 3)).sum()), int(((st == V.FOUND) & (ln >= 6)).sum())
+    print("%dx%d n %d: %d positions, %d wins, %d of length >= 3, %d of length >= 6, %d at the budget, nodes mean %.1f "
+          "max %d" % (S, S, n, idx.size, (st == V.FOUND).sum(), deep, deeper, (st == V.BUDGET).sum(), nd.mean(),
+                      nd.max()))
+    if G == ALL:
+        assert 900 <= idx.size <= 1200
+        assert (st == V.BUDGET).sum() <= 0.05 * idx.size
+        assert (deep >= 30 and deeper >= 5) if (S, n) != (6, 5) else deep >= 5
+    else:
+        assert idx.size == G and deep >= min(G, 3)
+    got = run_kernel(mods, b[idx], p[idx], n, DEPTH, NODES)
+    assert_equal(got, want, (S, n, G))
+
+
+# ---------------------------------------------------------------------------------------------- 2. limits
+@pytest.mark.parametrize("depth,nodes", [(1, NODES), (2, NODES), (16, NODES), (DEPTH, 1), (DEPTH, 8), (DEPTH, 64)])
+def test_limits(mods, depth, nodes):
+    b, p = pool(9, 5)
+    want = reference(9, 5, depth, nodes)
+    st, _, ln, nd = want
+    print("depth %d nodes %d: %d wins, longest %d, %d at the budget, most nodes %d" %
+          (depth, nodes, (st == V.FOUND).sum(), ln.max(), (st == V.BUDGET).sum(), nd.max()))
+    assert ln.max() <= depth and nd.max() <= nodes + 1 and (st == V.FOUND).any()
+    if depth == 1:
+        assert (nd == 1).all() and (ln[st == V.FOUND] == 1).all()
+    if nodes < NODES:
+        assert (st == V.BUDGET).any() and (nd[st == V.BUDGET] == nodes + 1).all()
+    assert_equal(run_kernel(mods, b, p, 5, depth, nodes), want, (depth, nodes))
+
+
+# ---------------------------------------------------------------------------------------------- 3. hand-built
+def test_kernel_on_the_hand_built_positions(mods):
+    for name, board, player, n, depth, nodes, want, want_nodes in TV.hand_built():
+        got = run_kernel(mods, board[None], np.array([player], np.int8), n, depth, nodes)
+        assert (int(got["status"][0]), int(got["move"][0]), int(got["length"][0])) == want, name
+        assert int(got["nodes"][0]) == V.solve(board, player, n, depth, nodes)[3], name
+        assert want_nodes is None or int(got["nodes"][0]) == want_nodes, name
+
+
+# ---------------------------------------------------------------------------------------------- 4. game / actions
+def test_skipped_boards_and_actions_in_place(mods):
+    idx = subset(9, 5, 65)
+    b, p = pool(9, 5)
+    b, p = b[idx], p[idx]
+    want = [w[idx] for w in reference(9, 5)]
+    G = idx.size
+    rs = np.random.RandomState(7)
+    game = np.arange(G, dtype=np.int32) * 3
+    out = np.zeros(G, bool)
+    out[rs.permutation(G)[:G // 3]] = True
+    out[np.flatnonzero(want[0] == V.FOUND)[:2]] = True  # boards with a win among the skipped ones
+    game[out] = -1 - rs.randint(0, 5, int(out.sum()))
+    before = (1000 + np.arange(G)).astype(np.int32)
+    got = run_kernel(mods, b, p, 5, DEPTH, NODES, game=game, actions=before)
+    won = (want[0] == V.FOUND) & ~out
+    assert won.any() and (~won & ~out).any()
+    assert (got["status"][out] == V.SKIPPED).all() and (got["move"][out] == -1).all()
+    assert (got["length"][out] == 0).all() and (got["nodes"][out] == 0).all()
+    for k, w in zip(("status", "move", "length", "nodes"), want):
+        assert np.array_equal(got[k][~out], w[~out]), k
+    assert np.array_equal(got["actions"], np.where(won, want[1], before))  # every other entry bit for bit
+    # no game array: every board is solved; lengths, nodes and actions are optional
+    got = run_kernel(mods, b, p, 5, DEPTH, NODES, outputs=False)
+    assert got["length"] is None and got["nodes"] is None and got["actions"] is None
+    assert np.array_equal(got["status"], want[0]) and np.array_equal(got["move"], want[1])
+    got = run_kernel(mods, b, p, 5, DEPTH, NODES, actions=before)
+    assert_equal(got, want, "actions without game")
+    assert np.array_equal(got["actions"], np.where(want[0] == V.FOUND, want[1], before))
+
+
+# ---------------------------------------------------------------------------------------------- 5. engine.vcf
+def test_engine_wrapper(mods):
+    m = mods
+    E = m["E"]
+    idx = subset(9, 5, 65)
+    b, p = pool(9, 5)
+    want = [w[idx] for w in reference(9, 5, DEPTH, 2048)]
+    bt = torch.from_numpy(b[idx].reshape(-1, 9, 9).copy()).cuda()
+    pt = torch.from_numpy(p[idx].copy()).cuda()
+    got = E.vcf(bt, pt)  # depth 10, 2,048 nodes
+    assert [t.dtype for t in got] == [torch.int8, torch.int32, torch.int32, torch.int32]
+    assert_equal(dict(zip(("status", "move", "length", "nodes"), (t.cpu().numpy() for t in got))), want, "engine.vcf")
+    act = torch.full((idx.size,), -5, dtype=torch.int32, device="cuda")
+    game = torch.arange(idx.size, dtype=torch.int32)
+    game[::2] = -1
+    st, mv, _, _ = E.vcf(bt, pt, depth=4, nodes=64, game=game, actions=act)
+    w4 = [w[idx] for w in reference(9, 5, 4, 64)]
+    live = (game >= 0).numpy()
+    assert np.array_equal(st.cpu().numpy(), np.where(live, w4[0], V.SKIPPED))
+    assert np.array_equal(act.cpu().numpy(), np.where(live & (w4[0] == V.FOUND), w4[1], -5))
+    small = TV.hand_built()[-3]  # n_in_row 4 on 6x6
+    got = E.vcf(torch.from_numpy(small[1][None]).cuda(), [small[2]], n_in_row=4)
+    assert (int(got[0][0]), int(got[1][0]), int(got[2][0])) == small[6]
+    with pytest.raises(m["L"].GmzError, match="gmz_game_vcf: max_depth"):
+        E.vcf(bt, pt, depth=17)
+    with pytest.raises(ValueError, match="actions"):
+        E.vcf(bt, pt, actions=act.cpu())
+
+
+# ---------------------------------------------------------------------------------------------- the matches
+N_OPENINGS = 6
+
+
+def _noise(m, A, key, ply, seed, out):
+    L = m["L"]
+    k = torch.tensor([key], dtype=torch.int32, device="cuda")
+    p = torch.tensor([ply], dtype=torch.int32, device="cuda")
+    L.check(m["lib"].gmz_gumbel_keyed(L.ptr(k), L.ptr(p), seed, 1, A, L.ptr(out), L.nbytes(out), L.stream_ptr()))
+    return out.cpu().numpy()[0]
+
+
+def _records(res):
+    return {2 * g.opening + (g.first_mover == "b"): (g.winner_colour, g.length, g.moves) for g in res.games}
+
+
+def _arena(m, cfg, sides, slots, book, seed, streams=1):
+    ar = m["AR"].Arena(cfg, sides[0], sides[1], slots, book, seed=seed, record_moves=True, streams=streams)
+    res = ar.run()
+    finished = int(ar.match.finished.cpu()[0])
+    ar.close()
+    return res, finished
+
+
+@functools.lru_cache(maxsize=None)
+def _model_match(seed, scale):
+    """anchor:vcf (A) against anchor:threat (B) on 9x9 by the model: ({game id: (winner, length, moves)}, solver
+    moves played).  Needs the GPU for the keyed noise rows only."""
+    import datou_gomoku_muzero_amd._lib as L
+    import datou_gomoku_muzero_amd.arena as AR
+    m = dict(L=L, lib=L.load())
+    book = AR.paired_openings(N_OPENINGS, 9, seed)
+    noise = torch.zeros(1, 81, dtype=torch.float64, device="cuda")
+    sides = [("vcf", scale, 10, 2048), ("threat", scale)]
+    out, solved = {}, 0
+    for t in range(N_OPENINGS):
+        for first in (0, 1):
+            w, moves, k = V.play_game(book[0][t].reshape(81), int(book[1][t]), [sides[first], sides[1 - first]],
+                                      lambda ply: _noise(m, 81, t, ply, seed, noise), 5)
+            out[2 * t + first] = (w, len(moves), moves)
+            solved += k
+    return out, solved
+
+
+# ---------------------------------------------------------------------------------------------- 6.
+@pytest.mark.parametrize("slots,streams", [(8, 1), (3, 1), (4, 2)])
+def test_vcf_against_threat_equals_the_model(mods, slots, streams):
+    m = mods
+    AR = m["AR"]
+    seed, scale = 5, 3e3
+    cfg = m["Cfg"](BOARD_SIZE=9, NUM_SIMULATIONS=16, NUM_RES_BLOCKS=2)
+    book = AR.paired_openings(N_OPENINGS, 9, seed)
+    want, solved = _model_match(seed, scale)
+    print("model: %d solver moves in %d games" % (solved, len(want)))
+    assert solved >= 3  # the solver's move was played, so the match is not the threat anchor's against itself
+    res, finished = _arena(m, cfg, [AR.AnchorPlayer("vcf", scale), AR.AnchorPlayer("threat", scale)], slots, book, seed,
+                           streams)
+    assert finished == 2 * N_OPENINGS == len(res.games)
+    rec = _records(res)
+    for gid, w in want.items():
+        assert rec[gid] == w, gid
+    assert res.moves_played == sum(g.length for g in res.games)
+
+
+# ---------------------------------------------------------------------------------------------- 7.
+SEED_NET = 0
+
+
+def _slow_match(m, cfg, net, anchor, book, seed):
+    """HashNet (A) against an anchor (B, a vcf_ref mover) one game at a time: the network's plies through a one-game
+    engine, the anchor's through the model on the same keyed noise row.  ({game id: (winner, length, moves)}, solver
+    moves played)."""
+    E = m["E"]
+    S = cfg.BOARD_SIZE
+    A = S * S
+    e = E.BatchedSelfPlayEngine(cfg, num_games=1, net=net, seed=seed)
+    boards, players, last, _ = book
+    noise = torch.zeros(1, A, dtype=torch.float64, device="cuda")
+    out, solved = {}, 0
+    for t in range(boards.shape[0]):
+        for first in (0, 1):
+            b, p, lm = boards[t].reshape(A).copy(), int(players[t]), int(last[t])
+            moves = []
+            while True:
+                row = _noise(m, A, t, len(moves), seed, noise)
+                if (first + len(moves)) % 2:
+                    a, by_solver = V.mover_move(b, p, cfg.N_IN_ROW, row, anchor)
+                    solved += by_solver
+                    assert a >= 0 and b[a] == 0
+                    b[a] = p
+                    s = p if R.wins(b.reshape(S, S), a, cfg.N_IN_ROW) else (2 if (b == 0).any() else 0)
+                else:
+                    e.set_positions(b.reshape(1, S, S), [p], [lm])
+                    _, _, act = e.search(gumbel=noise)
+                    st = e.play(reset_finished=False)
+                    a, s = int(act.cpu()[0]), int(st.cpu()[0])
+                    assert b[a] == 0
+                    b[a] = p
+                moves.append(a)
+                p, lm = -p, a
+                if s != 2:
+                    break
+            out[2 * t + first] = (s, len(moves), moves)
+    e.close()
+    return out, solved
+
+
+def test_vcf_against_a_network_equals_the_slow_path(mods):
+    m = mods
+    E, AR = m["E"], m["AR"]
+    cfg = m["Cfg"](BOARD_SIZE=6, NUM_SIMULATIONS=32, MCTS_IMPLEMENTATION="MuZero", NUM_RES_BLOCKS=2)
+    book = AR.paired_openings(N_OPENINGS, 6, SEED_NET)
+    anchor = AR.AnchorPlayer("vcf", depth=6, nodes=256)
+    slow, solved = _slow_match(m, cfg, E.HashNetBackend(E.hidden_slots(cfg, 1), 36), anchor.checked(), book, SEED_NET)
+    print("slow path: %d solver moves in %d games" % (solved, len(slow)))
+    res, finished = _arena(m, cfg, [E.HashNetBackend(E.hidden_slots(cfg, 4), 36), anchor], 4, book, SEED_NET)
+    assert finished == 2 * N_OPENINGS
+    rec = _records(res)
+    assert sorted(rec) == sorted(slow)
+    for gid, w in slow.items():
+        assert rec[gid] == w, gid
+
+
+# ---------------------------------------------------------------------------------------------- 8.
+def test_command_line_names_the_vcf_anchor(mods, capsys):
+    rc = mods["AR"].main(["--a", "anchor:vcf", "--b", "anchor:threat", "--games", "4", "--board-size", "6",
+                          "--anchor-depth", "6", "--anchor-nodes", "128", "--anchor-scale", "0.5", "--slots", "4"])
+    out = json.loads(capsys.readouterr().out.strip())
+    assert rc == 0 and out["a"] == "anchor:vcf" and out["b"] == "anchor:threat" and out["games"] == 4
+    with pytest.raises(ValueError, match="depth"):
+        mods["AR"].main(["--a", "anchor:vcf", "--b", "anchor:threat", "--games", "2", "--board-size", "6",
+                         "--anchor-depth", "17", "--slots", "2"])

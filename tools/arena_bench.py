@@ -3,7 +3,9 @@ against an anchor opponent, at the headline's shape (15x15, 400 simulations, 1,0
 beside ``python bench.py``'s self-play headline on the same GPU (profiles/arena.txt, profiles/arena_anchor.txt).
 
   python tools/arena_bench.py [--streams 1,2 --steps 10 --warmup 3 --rounds 2] [--b anchor:threat]
+  python tools/arena_bench.py --b anchor:vcf [--anchor-depth 10 --anchor-nodes 2048]
   python tools/arena_bench.py --anchor-launch 200      (the anchor launch alone, by event timing)
+  python tools/arena_bench.py --vcf-launch 50          (the solver launch alone, on positions of threat-anchor games)
 
 The book holds more openings than the timed plies can finish, so no slot idles; a move is counted from the
 statuses (arena's ``moves_played``).  Prints one JSON line per (round, streams)."""
@@ -22,8 +24,8 @@ from datou_gomoku_muzero_amd import arena as AR, engine as E, network as N, weig
 from datou_gomoku_muzero_amd.config import GmzConfig  # noqa: E402
 
 
-def measure(cfg, sd, slots, streams, steps, warmup, precision, seed, side_b="self"):
-    anchor = AR.anchor_from_name(side_b)
+def measure(cfg, sd, slots, streams, steps, warmup, precision, seed, side_b="self", depth=None, nodes=None):
+    anchor = AR.anchor_from_name(side_b, depth=depth, nodes=nodes)
     nets = [N.GomokuNetHip(sd, cfg, num_slots=E.hidden_slots(cfg, slots), max_rows=slots, precision=precision)
             for _ in range(1 if anchor else 2)]
     # 8 games per slot: against the threat anchor a game lasts some 8 plies, so the default 13 plies finish fewer
@@ -70,6 +72,43 @@ def anchor_launch(size, boards, reps, seed):
     return out
 
 
+def vcf_launch(size, boards, reps, seed, depth, nodes, scale=3e3):
+    """Microseconds per gmz_game_vcf launch on ``boards`` positions taken from games between two threat anchors
+    (noise scale 3e3, from the empty board, played by the numpy model tests/vcf_ref.py), by HIP events over ``reps``
+    launches; and the same launch on the slowest board alone, which bounds what one wave holds."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import vcf_ref  # the numpy model: its games are the positions (tests/test_vcf_gpu.py uses the same)
+    games, bb, pp = 0, np.zeros((0, size * size), np.int8), np.zeros(0, np.int8)
+    while bb.shape[0] < boards:
+        games += max(boards // 32, 1)
+        bb, pp = vcf_ref.threat_game_positions(size, 5, games, seed, scale)
+    b = torch.from_numpy(bb[:boards].reshape(boards, size, size).copy()).cuda()
+    p = torch.from_numpy(pp[:boards].copy()).cuda()
+    out = dict(size=size, boards=boards, reps=reps, depth=depth, nodes=nodes)
+
+    def timed(bb, pp, n):
+        for _ in range(3):
+            E.vcf(bb, pp, depth, nodes)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(n):
+            E.vcf(bb, pp, depth, nodes)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return round(1000.0 * ev[0].elapsed_time(ev[1]) / n, 2)
+
+    st, _, ln, nd = E.vcf(b, p, depth, nodes)
+    out["us_per_launch"] = timed(b, p, reps)
+    worst = int(nd.argmax())
+    out["us_slowest_board_alone"] = timed(b[worst:worst + 1], p[worst:worst + 1], reps)
+    nd = nd.cpu().numpy()
+    out.update(wins=int((st == 1).sum()), wins_len3=int(((st == 1) & (ln >= 3)).sum()), at_budget=int((st == 2).sum()),
+               nodes_mean=round(float(nd.mean()), 2), nodes_p99=int(np.percentile(nd, 99)), nodes_max=int(nd.max()))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=15)
@@ -82,11 +121,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--b", default="self", help="side B: 'self' (the network against itself), anchor:threat or "
-                                                "anchor:uniform")
+    ap.add_argument("--b", default="self", help="side B: 'self' (the network against itself), anchor:threat, "
+                                                "anchor:uniform or anchor:vcf")
     ap.add_argument("--anchor-launch", type=int, default=0, metavar="REPS",
                     help="time the anchor launch alone on --slots boards over REPS launches, and stop")
+    ap.add_argument("--anchor-depth", type=int, default=None, help="anchor:vcf: attacker moves looked ahead (10)")
+    ap.add_argument("--anchor-nodes", type=int, default=None, help="anchor:vcf: node budget per board (2048)")
+    ap.add_argument("--vcf-launch", type=int, default=0, metavar="REPS",
+                    help="time the solver launch alone on --slots positions over REPS launches, and stop")
     a = ap.parse_args()
+    if a.vcf_launch:
+        print(json.dumps(vcf_launch(a.size, a.slots, a.vcf_launch, a.seed, a.anchor_depth or E.VCF_DEPTH,
+                                    a.anchor_nodes or E.VCF_NODES)), flush=True)
+        return
     if a.anchor_launch:
         print(json.dumps(anchor_launch(a.size, a.slots, a.anchor_launch, a.seed)), flush=True)
         return
@@ -94,7 +141,8 @@ def main():
     sd = W.synthetic_state_dict(cfg, seed=a.seed, with_projection=False)
     for r in range(a.rounds):
         for s in [int(x) for x in a.streams.split(",")]:
-            out = measure(cfg, sd, a.slots, s, a.steps, a.warmup, a.precision, a.seed, a.b)
+            out = measure(cfg, sd, a.slots, s, a.steps, a.warmup, a.precision, a.seed, a.b, a.anchor_depth,
+                          a.anchor_nodes)
             out["round"] = r
             print(json.dumps(out), flush=True)
 
