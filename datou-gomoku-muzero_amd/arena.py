@@ -33,6 +33,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .openings import paired_openings  # noqa: F401  (the book's builder, numpy only)
+
 Z95 = 1.959963984540054  # the normal distribution's 97.5 % point
 
 
@@ -75,27 +77,6 @@ def naive_elo_interval(game_scores, z=Z95):
 
 
 # ---------------------------------------------------------------------------------------------- book
-def paired_openings(n, size, seed, stones=(2, 4, 6), n_in_row=5):
-    """A book of ``n`` openings: opening i holds stones[i % len(stones)] stones of alternating colour (black
-    first) on random cells, no n_in_row line (engine._place_stones), drawn from RandomState(seed + i).  Returns
-    (boards int8 [n,S,S], players int8 [n] = side to move, last_moves int32 [n], move_counts int32 [n])."""
-    from .engine import _place_stones
-    A = size * size
-    boards = np.zeros((n, size, size), np.int8)
-    players = np.ones(n, np.int8)
-    last = np.full(n, -1, np.int32)
-    counts = np.zeros(n, np.int32)
-    for i in range(n):
-        k = int(stones[i % len(stones)])
-        rs = np.random.RandomState((int(seed) + i) % (2 ** 32))
-        b, cells = _place_stones(rs, A, size, k, n_in_row)
-        boards[i] = b.reshape(size, size)
-        players[i] = 1 if k % 2 == 0 else -1
-        last[i] = cells[-1] if k else -1
-        counts[i] = k
-    return boards, players, last, counts
-
-
 def check_book(openings, cfg):
     """The book as four arrays, refused (ValueError) unless every opening leaves at least NUM_TOP_ACTIONS legal
     cells: for any such legal count the search's wave count is the empty board's, so a slot may start an opening
@@ -274,7 +255,7 @@ class Arena:
         if num_slots < streams or num_slots % streams:
             raise ValueError("Arena: num_slots must be a positive multiple of streams")
         import torch
-        self.torch = torch
+        self.torch, self.E = torch, E
         self.device = torch.device(device)
         self.seed, self.record_moves, self.parts = int(seed), bool(record_moves), int(streams)
         self.num_slots = int(num_slots)
@@ -293,11 +274,9 @@ class Arena:
     def _views(self, net_a, net_b):
         """Per engine the pair (A's backend, B's backend), None in an anchor's place: with two engines a view of
         each network per engine, with its own pool slice and workspace."""
-        from . import engine as E
         if self.parts == 1:
             return [tuple(None if a is not None else n for n, a in zip((net_a, net_b), self.anchors))]
-        cus = self.torch.cuda.get_device_properties(self.device).multi_processor_count
-        cap = max(cus // 2, cus - E.TOWER_FREE_CUS)
+        cap = self.E.tower_grid_cap(self.device)
         va, vb = [[None] * self.parts if a is not None else n.split(self.parts, cap)
                   for n, a in zip((net_a, net_b), self.anchors)]
         return [(va[i], vb[i]) for i in range(self.parts)]
@@ -325,17 +304,13 @@ class Arena:
 
     def start(self):
         """Fresh match buffers, and the slots filled with the first games: engine i's first mover is network i % 2."""
-        from . import engine as E
         torch = self.torch
-        m = self.match = E.MatchBuffers(*self.book, record_moves=self.record_moves, device=self.device)
+        m = self.match = self.E.MatchBuffers(*self.book, record_moves=self.record_moves, device=self.device)
         g = self.engines[0].G
         none = torch.full((g,), -1, dtype=torch.int32, device=self.device)
         self._main = torch.cuda.current_stream(self.device)
         if self.parts > 1:
-            ev = torch.cuda.Event()
-            ev.record(self._main)
-            for st in self.streams:
-                st.wait_event(ev)
+            self.E.fork_streams(self._main, self.streams)
         for i, e in enumerate(self.engines):
             e.finished_seen = e.moves_played = 0
             with self._ctx(i):
@@ -361,21 +336,13 @@ class Arena:
                     continue
                 e.net = self.nets[i][k]
                 e.set_simulations(self.sims[k])
-                gens.append((i, e.search_steps(self.gumbel[i], self.streams[i])))
-        live = list(gens)
-        while live:  # one wave of each engine in turn (as SplitSelfPlayEngine.search)
-            for item in list(live):
-                i, gen = item
-                with self._ctx(i):
-                    try:
-                        next(gen)
-                    except StopIteration:
-                        live.remove(item)
+                gens.append((self._ctx(i), e.search_steps(self.gumbel[i], self.streams[i])))
+        self.E.interleave(gens)  # one wave of each engine in turn
         for i, e in enumerate(self.engines):
             if actions[i] is not None:
                 # no search has read the last ply's status (a search does, to size its waves): read it before this
                 # ply's play_refill overwrites the pinned buffers, or the counters and the legal counts lose a ply
-                e._sync_status()
+                e.sync_status()
             with self._ctx(i):
                 e.play_refill(self.match, (self.ply + i + 1) % 2, action=actions[i], stream=self.streams[i])
         self.ply += 1
@@ -386,15 +353,11 @@ class Arena:
 
     def join(self):
         """The engines' streams joined into the caller's, and the last ply's statuses read."""
-        torch = self.torch
-        for st in self.streams:
-            if st is not None:
-                ev = torch.cuda.Event()
-                ev.record(st)
-                self._main.wait_event(ev)
+        if self.parts > 1:
+            self.E.join_streams(self._main, self.streams)
         for e in self.engines:
-            e._sync_status()
-        torch.cuda.synchronize(self.device)
+            e.sync_status()
+        self.torch.cuda.synchronize(self.device)
 
     def run(self):
         """Play the match to its end: the loop ends when the finished-games counter, read one ply behind, reaches

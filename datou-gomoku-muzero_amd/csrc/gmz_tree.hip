@@ -2104,43 +2104,31 @@ GMZ_EXPORT int gmz_engine_reset_games(gmz_engine *e, const uint8_t *mask, void *
 
 static inline dim3 wave_grid(const gmz_engine *e) { return dim3((e->D.G + 3) / 4); }
 
-// launch KERNEL<NJ> with NJ = ceil(A / 64) in {1, 2, 4, 6, 8}
-#define GMZ_LAUNCH_NJ(KERNEL, e, stream, ...)                                                                      \
-  do {                                                                                                             \
-    const int nj_ = ((e)->D.A + 63) / 64;                                                                          \
-    hipStream_t s_ = (hipStream_t)(stream);                                                                        \
-    if (nj_ <= 1) hipLaunchKernelGGL(KERNEL<1>, wave_grid(e), dim3(256), 0, s_, __VA_ARGS__);                     \
-    else if (nj_ <= 2) hipLaunchKernelGGL(KERNEL<2>, wave_grid(e), dim3(256), 0, s_, __VA_ARGS__);                \
-    else if (nj_ <= 4) hipLaunchKernelGGL(KERNEL<4>, wave_grid(e), dim3(256), 0, s_, __VA_ARGS__);                \
-    else if (nj_ <= 6) hipLaunchKernelGGL(KERNEL<6>, wave_grid(e), dim3(256), 0, s_, __VA_ARGS__);                \
-    else hipLaunchKernelGGL(KERNEL<8>, wave_grid(e), dim3(256), 0, s_, __VA_ARGS__);                              \
-    GMZ_LAUNCH_CHECK();                                                                                            \
-  } while (0)
-
-// k_select<NJ, HINT, AZ, CL> (descent prefetch hint, AlphaZero board replay and compact child lists
-// each compiled in or out)
-template <int NJ, bool H, bool AZ, bool CL>
-static int launch_select(gmz_engine *e, hipStream_t s, int32_t *in_slot, int32_t *action, int32_t *out_slot, float *obs) {
-  hipLaunchKernelGGL((k_select<NJ, H, AZ, CL>), wave_grid(e), dim3(256), 0, s, e->D, in_slot, action, out_slot, obs);
-  GMZ_LAUNCH_CHECK();
-  return 0;
+// The one variant dispatch of the engine's entry points (by_dtype's idiom, gmz_common.h).  by_nj: f(NJ tag) with
+// NJ = ceil(A / 64) in {1, 2, 4, 6, 8}, the actions per lane the kernels are compiled for.  by_variant: f(NJ tag, H,
+// AZ, CL) with the descent prefetch hint, the AlphaZero board replay and the compact child lists as bool tags, each
+// compiled in or out.  f returns what its launcher returns, and the value is handed on.
+template <typename F>
+static int by_nj(const gmz_engine *e, F &&f) {
+  const int nj = (e->D.A + 63) / 64;
+  if (nj <= 1) return f(std::integral_constant<int, 1>{});
+  if (nj <= 2) return f(std::integral_constant<int, 2>{});
+  if (nj <= 4) return f(std::integral_constant<int, 4>{});
+  if (nj <= 6) return f(std::integral_constant<int, 6>{});
+  return f(std::integral_constant<int, 8>{});
 }
-template <int NJ>
-static int launch_select_nj(gmz_engine *e, hipStream_t s, int32_t *in_slot, int32_t *action, int32_t *out_slot,
-                            float *obs) {
-  const bool h = !e->D.no_hint, az = e->D.mode == 0, cl = e->D.lists != 0;
-#define GMZ_SEL_CASE(H_, AZ_, CL_) \
-  if (h == H_ && az == AZ_ && cl == CL_) return launch_select<NJ, H_, AZ_, CL_>(e, s, in_slot, action, out_slot, obs)
-  GMZ_SEL_CASE(true, true, true);
-  GMZ_SEL_CASE(true, true, false);
-  GMZ_SEL_CASE(true, false, true);
-  GMZ_SEL_CASE(true, false, false);
-  GMZ_SEL_CASE(false, true, true);
-  GMZ_SEL_CASE(false, true, false);
-  GMZ_SEL_CASE(false, false, true);
-  GMZ_SEL_CASE(false, false, false);
-#undef GMZ_SEL_CASE
-  return fail("launch_select: unreachable");
+template <typename F>
+static int by_bool(bool b, F &&f) {
+  return b ? f(std::bool_constant<true>{}) : f(std::bool_constant<false>{});
+}
+template <typename F>
+static int by_variant(const gmz_engine *e, F &&f) {
+  const Dev &D = e->D;
+  return by_nj(e, [&](auto nj) {
+    return by_bool(!D.no_hint, [&](auto h) {
+      return by_bool(D.mode == 0, [&](auto az) { return by_bool(D.lists != 0, [&](auto cl) { return f(nj, h, az, cl); }); });
+    });
+  });
 }
 
 // k_expand_select<NJ, H, AZ, CL, WPB>: WPB = 1 when the games outnumber the variant's resident waves
@@ -2176,49 +2164,37 @@ static int launch_expand_select(gmz_engine *e, hipStream_t s, const float *logit
   return 0;
 }
 
-template <int NJ>
-static int launch_expand_select_nj(gmz_engine *e, hipStream_t s, const float *logits, const float *value,
-                                   const float *reward, int32_t *in_slot, int32_t *action, int32_t *out_slot, float *obs) {
-  const bool h = !e->D.no_hint, az = e->D.mode == 0, cl = e->D.lists != 0;
-#define GMZ_ES_CASE(H_, AZ_, CL_)        \
-  if (h == H_ && az == AZ_ && cl == CL_) \
-  return launch_expand_select<NJ, H_, AZ_, CL_>(e, s, logits, value, reward, in_slot, action, out_slot, obs)
-  GMZ_ES_CASE(true, true, true);
-  GMZ_ES_CASE(true, true, false);
-  GMZ_ES_CASE(true, false, true);
-  GMZ_ES_CASE(true, false, false);
-  GMZ_ES_CASE(false, true, true);
-  GMZ_ES_CASE(false, true, false);
-  GMZ_ES_CASE(false, false, true);
-  GMZ_ES_CASE(false, false, false);
-#undef GMZ_ES_CASE
-  return fail("launch_expand_select: unreachable");
-}
-
 GMZ_EXPORT int gmz_engine_begin_move(gmz_engine *e, const double *gumbel, uint64_t seed, float *obs, void *stream) {
   if (!e || !obs) return fail("gmz_engine_begin_move: null argument");
   const uint32_t ctr = e->counter++;
-  GMZ_LAUNCH_NJ(k_begin_move, e, stream, e->D, gumbel, seed, ctr, obs, e->active, e->budget);
-  return 0;
+  return by_nj(e, [&](auto nj) {
+    hipLaunchKernelGGL(k_begin_move<decltype(nj)::value>, wave_grid(e), dim3(256), 0, (hipStream_t)stream, e->D, gumbel,
+                       seed, ctr, obs, e->active, e->budget);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_engine_set_root(gmz_engine *e, const float *logits, const float *value, void *stream) {
   if (!e || !logits || !value) return fail("gmz_engine_set_root: null argument");
-  GMZ_LAUNCH_NJ(k_set_root, e, stream, e->D, logits, value);
-  return 0;
+  return by_nj(e, [&](auto nj) {
+    hipLaunchKernelGGL(k_set_root<decltype(nj)::value>, wave_grid(e), dim3(256), 0, (hipStream_t)stream, e->D, logits,
+                       value);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_engine_select(gmz_engine *e, int32_t *in_slot, int32_t *action, int32_t *out_slot, float *obs,
                                  void *stream) {
   if (!e || !in_slot || !action || !out_slot) return fail("gmz_engine_select: null argument");
   if (e->D.mode == 0 && !obs) return fail("gmz_engine_select: AlphaZero mode needs obs");
-  hipStream_t s = (hipStream_t)stream;
-  const int nj = (e->D.A + 63) / 64;
-  if (nj <= 1) return launch_select_nj<1>(e, s, in_slot, action, out_slot, obs);
-  if (nj <= 2) return launch_select_nj<2>(e, s, in_slot, action, out_slot, obs);
-  if (nj <= 4) return launch_select_nj<4>(e, s, in_slot, action, out_slot, obs);
-  if (nj <= 6) return launch_select_nj<6>(e, s, in_slot, action, out_slot, obs);
-  return launch_select_nj<8>(e, s, in_slot, action, out_slot, obs);
+  return by_variant(e, [&](auto nj, auto h, auto az, auto cl) {
+    hipLaunchKernelGGL((k_select<decltype(nj)::value, decltype(h)::value, decltype(az)::value, decltype(cl)::value>),
+                       wave_grid(e), dim3(256), 0, (hipStream_t)stream, e->D, in_slot, action, out_slot, obs);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_engine_expand_backup(gmz_engine *e, const float *logits, const float *value, const float *reward,
@@ -2226,8 +2202,12 @@ GMZ_EXPORT int gmz_engine_expand_backup(gmz_engine *e, const float *logits, cons
   if (!e || !logits || !value) return fail("gmz_engine_expand_backup: null argument");
   if (e->D.mode == 1 && !reward) return fail("gmz_engine_expand_backup: MuZero mode needs reward");
   const float *rw = e->D.mode == 1 ? reward : nullptr;
-  GMZ_LAUNCH_NJ(k_expand_backup, e, stream, e->D, logits, value, rw);
-  return 0;
+  return by_nj(e, [&](auto nj) {
+    hipLaunchKernelGGL(k_expand_backup<decltype(nj)::value>, wave_grid(e), dim3(256), 0, (hipStream_t)stream, e->D,
+                       logits, value, rw);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_engine_expand_backup_select(gmz_engine *e, const float *logits, const float *value,
@@ -2238,13 +2218,10 @@ GMZ_EXPORT int gmz_engine_expand_backup_select(gmz_engine *e, const float *logit
   if (e->D.mode == 1 && !reward) return fail("gmz_engine_expand_backup_select: MuZero mode needs reward");
   if (e->D.mode == 0 && !obs) return fail("gmz_engine_expand_backup_select: AlphaZero mode needs obs");
   const float *rw = e->D.mode == 1 ? reward : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  const int nj = (e->D.A + 63) / 64;
-  if (nj <= 1) return launch_expand_select_nj<1>(e, s, logits, value, rw, in_slot, action, out_slot, obs);
-  if (nj <= 2) return launch_expand_select_nj<2>(e, s, logits, value, rw, in_slot, action, out_slot, obs);
-  if (nj <= 4) return launch_expand_select_nj<4>(e, s, logits, value, rw, in_slot, action, out_slot, obs);
-  if (nj <= 6) return launch_expand_select_nj<6>(e, s, logits, value, rw, in_slot, action, out_slot, obs);
-  return launch_expand_select_nj<8>(e, s, logits, value, rw, in_slot, action, out_slot, obs);
+  return by_variant(e, [&](auto nj, auto h, auto az, auto cl) {
+    return launch_expand_select<decltype(nj)::value, decltype(h)::value, decltype(az)::value, decltype(cl)::value>(
+        e, (hipStream_t)stream, logits, value, rw, in_slot, action, out_slot, obs);
+  });
 }
 
 GMZ_EXPORT int gmz_engine_pending_waves(gmz_engine *e, int32_t *out) {
@@ -2316,8 +2293,12 @@ GMZ_EXPORT int gmz_engine_waves_for_budgets(const gmz_engine_cfg *cfg, const int
 
 GMZ_EXPORT int gmz_engine_finish_move(gmz_engine *e, double *policy, float *value, int32_t *action, void *stream) {
   if (!e || !policy || !value || !action) return fail("gmz_engine_finish_move: null argument");
-  GMZ_LAUNCH_NJ(k_finish, e, stream, e->D, policy, value, action);
-  return 0;
+  return by_nj(e, [&](auto nj) {
+    hipLaunchKernelGGL(k_finish<decltype(nj)::value>, wave_grid(e), dim3(256), 0, (hipStream_t)stream, e->D, policy,
+                       value, action);
+    GMZ_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 GMZ_EXPORT int gmz_engine_play(gmz_engine *e, const int32_t *action, int8_t *status, int reset_finished, void *stream) {

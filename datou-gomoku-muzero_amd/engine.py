@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from .config import from_any
 from ._lib import GmzError, check, ptr
+from .openings import _has_five, _place_stones, random_openings, seeded_openings  # noqa: F401  (re-exported)
 
 
 class HashNetBackend:
@@ -56,6 +57,29 @@ class HashNetBackend:
         check(_lib.load().gmz_hashnet_recurrent(ptr(self.pool), ptr(in_slot), ptr(action), ptr(out_slot),
                                                 in_slot.shape[0], self.A, ptr(logits), ptr(value), ptr(reward),
                                                 stream))
+
+
+class _PinnedPair:
+    """Two pinned host buffers that take turns carrying a small array to one device tensor with no host wait: a
+    slot is written again only after its own last copy (two uploads ago: long done) has finished."""
+
+    def __init__(self, shape, dtype):
+        self.host = [torch.zeros(shape, dtype=dtype).pin_memory() for _ in range(2)]
+        self.events = [None, None]
+        self.flip = 0
+
+    def upload(self, values, dev, stream=None):
+        """``values`` (a numpy array of the buffers' shape) into ``dev`` on ``stream`` (None: the current one)."""
+        i = self.flip
+        self.flip ^= 1
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        self.host[i].numpy()[:] = values
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            dev.copy_(self.host[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.events[i] = ev
 
 
 class BatchedSelfPlayEngine:
@@ -94,9 +118,7 @@ class BatchedSelfPlayEngine:
         # bit 3 compact child lists for non-root nodes; bit 4 two waves per game
         flags = ((0 if descent_hint else 1) | {None: 0, 4: 2, 1: 4}[wpb] | (8 if layout == "lists" else 0)
                  | (16 if self.pair else 0))
-        self.ecfg = _lib.EngineCfg(self.G, c.BOARD_SIZE, c.N_IN_ROW, c.NUM_SIMULATIONS, c.NUM_TOP_ACTIONS, self.mode,
-                                   int(c.C_VISIT), flags, float(c.C_SCALE),
-                                   float(c.VALUE_MINMAX_DELTA), float(c.DISCOUNT), int(game_offset))
+        self.ecfg = engine_cfg(c, self.G, flags, game_offset)
         h = ctypes.c_void_p()
         check(self.lib.gmz_engine_create(ctypes.byref(self.ecfg), ctypes.byref(h)))
         self.handle = h
@@ -124,9 +146,7 @@ class BatchedSelfPlayEngine:
         self.hidden_budget = self._hb_dev[G:]
         self.root_slot.copy_(torch.arange(G, dtype=i32, device=dev) * self.slots_per_game)
         self.hidden_budget.fill_(self.slots_per_game)
-        self._hb_host = [torch.zeros(2 * G, dtype=i32).pin_memory() for _ in range(2)]
-        self._hb_events = [None, None]
-        self._hb_flip = 0
+        self._hb_stage = _PinnedPair(2 * G, i32)
         self._hb_last = None  # the bases last handed to the engine (host copy)
         self.hidden_slots_used = 0
         self.policy = torch.zeros(G, A, dtype=torch.float64, device=dev)
@@ -139,9 +159,7 @@ class BatchedSelfPlayEngine:
         self._n_legal = np.full(G, A, dtype=np.int32)
         self._active = None  # host copy of set_active's mask (None: every game is searched)
         self._budgets = None  # host copy of set_budgets' simulations per game (None: every game the engine's)
-        self._bud_dev = None  # its device copy and the pinned staging pair of the uploads (made at the first call)
-        self._bud_host = self._bud_events = None
-        self._bud_flip = 0
+        self._bud_dev = self._bud_stage = None  # its device copy and the staging pair (made at the first call)
         self._refill = None  # play_refill's slot arrays and pinned read-back buffers (arena)
         self._refill_pending = False
         self._state_ptrs = None  # device pointers of the engine-owned game state (anchor_move, vcf_move)
@@ -291,18 +309,8 @@ class BatchedSelfPlayEngine:
             return  # the engine holds these already
         if self._bud_dev is None:
             self._bud_dev = torch.empty(self.G, dtype=torch.int32, device=self.device)
-            self._bud_host = [torch.zeros(self.G, dtype=torch.int32).pin_memory() for _ in range(2)]
-            self._bud_events = [None, None]
-        i = self._bud_flip
-        self._bud_flip ^= 1
-        if self._bud_events[i] is not None:
-            self._bud_events[i].synchronize()  # (an upload two calls ago: long done)
-        self._bud_host[i].numpy()[:] = a
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            self._bud_dev.copy_(self._bud_host[i], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        self._bud_events[i] = ev
+            self._bud_stage = _PinnedPair(self.G, torch.int32)
+        self._bud_stage.upload(a, self._bud_dev, stream)
         check(self.lib.gmz_engine_set_budgets(self.handle, ptr(self._bud_dev), _lib.nbytes(self._bud_dev), s))
         self._budgets = a
 
@@ -344,7 +352,9 @@ class BatchedSelfPlayEngine:
         check(self.lib.gmz_engine_reset_games(self.handle, ptr(m), self._stream()))
 
     # ------------------------------------------------------------------ search
-    def _sync_status(self):
+    def sync_status(self):
+        """Wait for the last play's status read-back (if one is pending): raises on the engine's error bits, and
+        brings the legal counts (and play_refill's counters) up to date.  search_steps calls it."""
         if self._status_event is not None:
             self._status_event.synchronize()
             err = int(self._err_host[0])
@@ -411,18 +421,7 @@ class BatchedSelfPlayEngine:
         if hasattr(self.net, "ensure_slots"):
             self.net.ensure_slots(total, stream)
         self._hb_net = self.net
-        i = self._hb_flip
-        self._hb_flip ^= 1
-        if self._hb_events[i] is not None:
-            self._hb_events[i].synchronize()  # (a copy two placements ago: long done)
-        hb = self._hb_host[i].numpy()
-        hb[:self.G] = base
-        hb[self.G:] = need
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            self._hb_dev.copy_(self._hb_host[i], non_blocking=True)  # on the search's stream
-            ev = torch.cuda.Event()
-            ev.record()
-        self._hb_events[i] = ev
+        self._hb_stage.upload(key, self._hb_dev, stream)  # on the search's stream
         check(self.lib.gmz_engine_set_hidden_bases(self.handle, ptr(self.root_slot), s))
         check(self.lib.gmz_engine_set_hidden_budget(self.handle, ptr(self.hidden_budget), s))
         self._hb_last = key
@@ -467,7 +466,7 @@ class BatchedSelfPlayEngine:
         check(L.gmz_engine_begin_move(self.handle, ptr(g), self.seed, ptr(self.obs), s))
         self.net.initial(self.obs, self.root_slot, self.logits, self.value, s)
         check(L.gmz_engine_set_root(self.handle, ptr(self.logits), ptr(self.value), s))
-        self._sync_status()  # previous move's status → legal counts (overlaps the root inference)
+        self.sync_status()  # previous move's status → legal counts (overlaps the root inference)
         waves = self.waves_needed()
         self.waves_last = waves
         rw = ptr(self.reward) if self.mode == 1 else None
@@ -501,13 +500,18 @@ class BatchedSelfPlayEngine:
         s = self._stream(stream)
         a = self.action if action is None else torch.as_tensor(action, dtype=torch.int32).to(self.device)
         check(self.lib.gmz_engine_play(self.handle, ptr(a), ptr(self.status), 1 if reset_finished else 0, s))
+        self._post_status(stream)
+        self._last_reset = bool(reset_finished)
+        return self.status
+
+    def _post_status(self, stream):
+        """The status and the engine's error word to their pinned buffers behind a play launch, and the event that
+        sync_status waits for."""
         self._status_host.copy_(self.status, non_blocking=True)
-        check(self.lib.gmz_engine_errors_async(self.handle, ptr(self._err_host), s))
+        check(self.lib.gmz_engine_errors_async(self.handle, ptr(self._err_host), self._stream(stream)))
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream() if stream is None else stream)
         self._status_event = ev
-        self._last_reset = bool(reset_finished)
-        return self.status
 
     def play_refill(self, match, next_net, action=None, stream=None):
         """play(reset_finished=False) plus an arena's bookkeeping in one launch (gmz_engine_play_refill):
@@ -540,11 +544,7 @@ class BatchedSelfPlayEngine:
             ptr(m.winner), ptr(m.length), ptr(m.moves), m.A, m.winner.numel(), ptr(m.finished), s))
         r["back"][G:].copy_(m.finished, non_blocking=True)
         r["host"].copy_(r["back"], non_blocking=True)
-        self._status_host.copy_(self.status, non_blocking=True)
-        check(self.lib.gmz_engine_errors_async(self.handle, ptr(self._err_host), s))
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream() if stream is None else stream)
-        self._status_event = ev
+        self._post_status(stream)
         self._refill_pending = True
         self._active = None  # the device mask is the slots' own now; idle slots report 0 legal cells
         self._last_reset = False
@@ -558,21 +558,27 @@ class BatchedSelfPlayEngine:
                                         _lib.nbytes(out), self._stream(stream)))
         return out
 
+    def _game_ptrs(self):
+        """Device pointers of the engine's own boards and players (fetched once), and of play_refill's ``game`` row
+        (None on an engine that play_refill does not drive)."""
+        if self._state_ptrs is None:
+            p = [ctypes.c_void_p() for _ in range(4)]
+            check(self.lib.gmz_engine_game_state(self.handle, *[ctypes.byref(x) for x in p]))
+            self._state_ptrs = p
+        game = self._refill["game"] if self._refill is not None else None
+        return self._state_ptrs[0], self._state_ptrs[1], ptr(game)
+
     def anchor_move(self, noise=None, kind="threat", scale=0.0, stream=None):
         """An anchor opponent's move (gmz_game_anchor_move, see ``anchor_move``) for the side to move on the
         engine's own device boards, in one launch on ``stream`` with no host wait: into ``self.action``, which is
         returned and which play_refill(action=...) takes.  ``noise``: f64[G,A] on the device (keyed_gumbel's) or
         None.  On an engine that play_refill drives, an idle slot gets -1."""
-        if self._state_ptrs is None:
-            p = [ctypes.c_void_p() for _ in range(4)]
-            check(self.lib.gmz_engine_game_state(self.handle, *[ctypes.byref(x) for x in p]))
-            self._state_ptrs = p
         if noise is not None and (not torch.is_tensor(noise) or noise.dtype != torch.float64
                                   or noise.device.type != self.device.type or not noise.is_contiguous()):
             raise ValueError("anchor_move: noise must be a contiguous float64 tensor on %s" % self.device)
-        game = self._refill["game"] if self._refill is not None else None
+        boards, players, game = self._game_ptrs()
         check(self.lib.gmz_game_anchor_move(
-            self._state_ptrs[0], self._state_ptrs[1], ptr(game), ptr(noise), _lib.nbytes(noise), self.G, self.size,
+            boards, players, game, ptr(noise), _lib.nbytes(noise), self.G, self.size,
             self.cfg.N_IN_ROW, anchor_kind(kind), float(scale), ptr(self.action), _lib.nbytes(self.action), None, 0,
             self._stream(stream)))
         return self.action
@@ -582,16 +588,12 @@ class BatchedSelfPlayEngine:
         in one launch on ``stream`` with no host wait: where it finds a win its move replaces the entry of
         ``self.action`` (after anchor_move: the threat rule's move), every other entry stays.  Returns
         ``self.action``; the statuses and moves of the launch stay in ``self.vcf_status`` / ``self.vcf_moves``."""
-        if self._state_ptrs is None:
-            p = [ctypes.c_void_p() for _ in range(4)]
-            check(self.lib.gmz_engine_game_state(self.handle, *[ctypes.byref(x) for x in p]))
-            self._state_ptrs = p
         if self.vcf_status is None:
             self.vcf_status = torch.zeros(self.G, dtype=torch.int8, device=self.device)
             self.vcf_moves = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
-        game = self._refill["game"] if self._refill is not None else None
+        boards, players, game = self._game_ptrs()
         check(self.lib.gmz_game_vcf(
-            self._state_ptrs[0], self._state_ptrs[1], ptr(game), self.G, self.size, self.cfg.N_IN_ROW,
+            boards, players, game, self.G, self.size, self.cfg.N_IN_ROW,
             VCF_DEPTH if depth is None else int(depth), VCF_NODES if nodes is None else int(nodes),
             ptr(self.vcf_status), _lib.nbytes(self.vcf_status), ptr(self.vcf_moves), _lib.nbytes(self.vcf_moves),
             None, 0, None, 0, ptr(self.action), _lib.nbytes(self.action), self._stream(stream)))
@@ -667,8 +669,7 @@ class SplitSelfPlayEngine:
         # descent_hint / layout None: each part's defaults — the cached-exp softmax in every part, as one
         # engine with every game (the layout may differ per part: results are identical)
         if max_grid is None:  # every CU but TOWER_FREE_CUS for the other part's tree and head kernels
-            cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-            max_grid = max(cus // 2, cus - TOWER_FREE_CUS) if parts > 1 else 0
+            max_grid = tower_grid_cap(self.device) if parts > 1 else 0
         if net is None:
             net = HashNetBackend(hidden_slots(c, G), self.A, device)
         self.net = net
@@ -688,20 +689,10 @@ class SplitSelfPlayEngine:
             e.policy, e.root_value, e.action, e.status = self.policy[sl], self.root_value[sl], self.action[sl], self.status[sl]
         self.waves_last = 0
 
-    # ------------------------------------------------------------------ streams
     def _fork(self, stream=None):
         main = stream if stream is not None else torch.cuda.current_stream(self.device)
-        ev = torch.cuda.Event()
-        ev.record(main)
-        for st in self.streams:
-            st.wait_event(ev)
+        fork_streams(main, self.streams)
         return main
-
-    def _join(self, main):
-        for st in self.streams:
-            ev = torch.cuda.Event()
-            ev.record(st)
-            main.wait_event(ev)
 
     def _rows(self, x, i):
         return None if x is None else x[i * self.g:(i + 1) * self.g]
@@ -716,17 +707,9 @@ class SplitSelfPlayEngine:
         if gumbel is not None:  # to the device on the caller's stream, before the fork
             g = torch.as_tensor(gumbel, dtype=torch.float64).to(self.device).contiguous()
         main = self._fork(stream)
-        gens = [e.search_steps(self._rows(g, i), st) for i, (e, st) in enumerate(zip(self.engines, self.streams))]
-        live = list(zip(gens, self.streams))
-        while live:  # one wave of each part in turn
-            for item in list(live):
-                gen, st = item
-                with torch.cuda.stream(st):
-                    try:
-                        next(gen)
-                    except StopIteration:
-                        live.remove(item)
-        self._join(main)
+        interleave([(torch.cuda.stream(st), e.search_steps(self._rows(g, i), st))  # one wave of each part in turn
+                    for i, (e, st) in enumerate(zip(self.engines, self.streams))])
+        join_streams(main, self.streams)
         self.waves_last = max(e.waves_last for e in self.engines)
         return self.policy, self.root_value, self.action
 
@@ -736,7 +719,7 @@ class SplitSelfPlayEngine:
         for i, (e, st) in enumerate(zip(self.engines, self.streams)):
             with torch.cuda.stream(st):
                 e.play(self._rows(a, i), reset_finished)
-        self._join(main)
+        join_streams(main, self.streams)
         return self.status
 
     def set_active(self, mask=None):
@@ -813,20 +796,30 @@ class MatchBuffers:
         self.moves = torch.full((2 * n, self.A), -1, dtype=torch.int16, device=dev) if record_moves else None
 
 
-def slot_need_table(ecfg, A, mode, lib=None):
-    """Hidden-state slots one game's search can use, by legal-move count L = 0..A: MuZero creates the
+def engine_cfg(c, num_games, flags=0, game_offset=0):
+    """The gmz_engine_cfg (include/gmz.h) of ``num_games`` games under the configuration ``c``."""
+    mode = 1 if c.MCTS_IMPLEMENTATION == "MuZero" else 0
+    return _lib.EngineCfg(int(num_games), c.BOARD_SIZE, c.N_IN_ROW, c.NUM_SIMULATIONS, c.NUM_TOP_ACTIONS, mode,
+                          int(c.C_VISIT), flags, float(c.C_SCALE), float(c.VALUE_MINMAX_DELTA), float(c.DISCOUNT),
+                          int(game_offset))
+
+
+def slot_need(ecfg, mode, L, lib=None):
+    """Hidden-state slots one game's search can use at the legal-move count ``L``: MuZero creates the
     root and one node per wave (mcts.py:320-350), i.e. gmz_engine_waves_for_legal(L) + 1, plus one
     spare; AlphaZero one node per simulation (mcts.py:233-268): num_simulations + 2."""
-    L = lib if lib is not None else _lib.load()
-    tab = np.full(A + 1, ecfg.num_simulations + 2, np.int64)
-    if mode == 1:
-        out = ctypes.c_int32()
-        for n in range(A + 1):
-            one = np.array([n], np.int32)
-            check(L.gmz_engine_waves_for_legal(ctypes.byref(ecfg), one.ctypes.data_as(ctypes.c_void_p), 1,
-                                               ctypes.byref(out)))
-            tab[n] = out.value + 2
-    return tab
+    if mode == 0:
+        return ecfg.num_simulations + 2
+    out = ctypes.c_int32()
+    one = np.array([L], np.int32)
+    check((lib if lib is not None else _lib.load()).gmz_engine_waves_for_legal(
+        ctypes.byref(ecfg), one.ctypes.data_as(ctypes.c_void_p), 1, ctypes.byref(out)))
+    return out.value + 2
+
+
+def slot_need_table(ecfg, A, mode, lib=None):
+    """slot_need by legal-move count L = 0..A (int64 [A + 1])."""
+    return np.array([slot_need(ecfg, mode, n, lib) for n in range(A + 1)], np.int64)
 
 
 def hidden_slots(cfg, num_games):
@@ -834,17 +827,44 @@ def hidden_slots(cfg, num_games):
     count >= NUM_TOP_ACTIONS (MuZero C2: 102 slots per game instead of NUM_SIMULATIONS + 2 = 402; the
     pool grows if late-game positions need more, BatchedSelfPlayEngine._place_hidden)."""
     c = from_any(cfg)
-    A = c.ACTION_SPACE_SIZE
-    mode = 1 if c.MCTS_IMPLEMENTATION == "MuZero" else 0
-    ecfg = _lib.EngineCfg(1, c.BOARD_SIZE, c.N_IN_ROW, c.NUM_SIMULATIONS, c.NUM_TOP_ACTIONS, mode, int(c.C_VISIT), 0,
-                          float(c.C_SCALE), float(c.VALUE_MINMAX_DELTA), float(c.DISCOUNT), 0)
-    if mode == 0:
-        return int(num_games) * (c.NUM_SIMULATIONS + 2)
-    out = ctypes.c_int32()
-    one = np.array([A], np.int32)
-    check(_lib.load().gmz_engine_waves_for_legal(ctypes.byref(ecfg), one.ctypes.data_as(ctypes.c_void_p), 1,
-                                                 ctypes.byref(out)))
-    return int(num_games) * (out.value + 2)
+    ecfg = engine_cfg(c, 1)
+    return int(num_games) * slot_need(ecfg, ecfg.mode, c.ACTION_SPACE_SIZE)
+
+
+def tower_grid_cap(device):
+    """The tower grid of one part of a two-stream engine or arena: every CU but TOWER_FREE_CUS (at least half)."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return max(cus // 2, cus - TOWER_FREE_CUS)
+
+
+def fork_streams(main, streams):
+    """Every stream of ``streams`` waits for what ``main`` holds now."""
+    ev = torch.cuda.Event()
+    ev.record(main)
+    for st in streams:
+        st.wait_event(ev)
+
+
+def join_streams(main, streams):
+    """``main`` waits for what every stream of ``streams`` holds now."""
+    for st in streams:
+        ev = torch.cuda.Event()
+        ev.record(st)
+        main.wait_event(ev)
+
+
+def interleave(items):
+    """Drive (context, generator) pairs one next() each in turn, each under its context, until all are exhausted
+    (search_steps generators on different streams: their waves alternate on the host)."""
+    live = list(items)
+    while live:
+        for item in list(live):
+            ctx, gen = item
+            with ctx:
+                try:
+                    next(gen)
+                except StopIteration:
+                    live.remove(item)
 
 
 _ENGINE_STREAMS = {}
@@ -902,6 +922,21 @@ def make_engine(cfg=None, num_games=1, net=None, device="cuda", seed=0, streams=
     return BatchedSelfPlayEngine(cfg, num_games, net, device, seed, **kw)
 
 
+def _board_args(who, boards, players, game=None, checked=True):
+    """(boards, players, game) of the free functions below as contiguous tensors on the boards' device, with G and
+    S: (b, p, gm or None, G, S).  ``checked``: ValueError under the caller's name ``who`` unless the boards are int8
+    [G, S, S] and players (and game) hold G entries."""
+    b = torch.as_tensor(boards).contiguous()
+    if checked and (b.dtype != torch.int8 or b.dim() < 2):
+        raise ValueError("%s: boards must be int8 [G, S, S]" % who)
+    G, S = b.shape[0], b.shape[-1]
+    p = torch.as_tensor(players, dtype=torch.int8).to(b.device).contiguous()
+    gm = None if game is None else torch.as_tensor(game, dtype=torch.int32).to(b.device).contiguous()
+    if checked and (b.numel() != G * S * S or p.numel() != G or (gm is not None and gm.numel() != G)):
+        raise ValueError("%s: expected boards [G, S, S] with players (and game) of G entries" % who)
+    return b, p, gm, G, S
+
+
 def winning_scan(boards, players, actions=None, n_in_row=5, counters=None, stream=None, lib=None):
     """Batched workers.py:49-123 ``find_winning_moves_rebuilt`` (``gmz_game_winning_scan``).
 
@@ -910,9 +945,7 @@ def winning_scan(boards, players, actions=None, n_in_row=5, counters=None, strea
     ``actions`` int32[G] and ``counters`` = (missed_fives, missed_totals) int32[G] device tensors:
     adds the workers.py:191-203 missed-win counts of this position (action < 0: game skipped)."""
     L = lib if lib is not None else _lib.load()
-    b = torch.as_tensor(boards).contiguous()
-    G, S = b.shape[0], b.shape[-1]
-    p = torch.as_tensor(players, dtype=torch.int8).to(b.device).contiguous()
+    b, p, _, G, S = _board_args("winning_scan", boards, players, checked=False)
     cls, mf, mt, a = None, None, None, None
     if actions is None:
         cls = torch.zeros(G, S * S, dtype=torch.uint8, device=b.device)
@@ -946,15 +979,8 @@ def anchor_move(boards, players, noise=None, kind="threat", scale=0.0, n_in_row=
     actions int32[G] (-1: full board or left out), or (actions, scores int64[G,S*S]) with ``scores`` (-1 for an
     occupied cell)."""
     L = _lib.load()
-    b = torch.as_tensor(boards).contiguous()
-    if b.dtype != torch.int8 or b.dim() < 2:
-        raise ValueError("anchor_move: boards must be int8 [G, S, S]")
-    G, S = b.shape[0], b.shape[-1]
-    p = torch.as_tensor(players, dtype=torch.int8).to(b.device).contiguous()
+    b, p, gm, G, S = _board_args("anchor_move", boards, players, game)
     nz = None if noise is None else torch.as_tensor(noise, dtype=torch.float64).to(b.device).contiguous()
-    gm = None if game is None else torch.as_tensor(game, dtype=torch.int32).to(b.device).contiguous()
-    if b.numel() != G * S * S or p.numel() != G or (gm is not None and gm.numel() != G):
-        raise ValueError("anchor_move: expected boards [G, S, S] with players (and game) of G entries")
     act = torch.empty(G, dtype=torch.int32, device=b.device)
     sc = torch.empty(G, S * S, dtype=torch.int64, device=b.device) if scores else None
     check(L.gmz_game_anchor_move(ptr(b), ptr(p), ptr(gm), ptr(nz), _lib.nbytes(nz), G, S, int(n_in_row),
@@ -976,14 +1002,7 @@ def vcf(boards, players, depth=VCF_DEPTH, nodes=VCF_NODES, game=None, actions=No
     and stays as it is everywhere else.  Returns (status int8[G]: 0 none, 1 found, 2 node budget used up, 3 skipped;
     move int32[G], -1 unless status is 1; length int32[G], the attacker moves of the line; nodes int32[G])."""
     L = _lib.load()
-    b = torch.as_tensor(boards).contiguous()
-    if b.dtype != torch.int8 or b.dim() < 2:
-        raise ValueError("vcf: boards must be int8 [G, S, S]")
-    G, S = b.shape[0], b.shape[-1]
-    p = torch.as_tensor(players, dtype=torch.int8).to(b.device).contiguous()
-    gm = None if game is None else torch.as_tensor(game, dtype=torch.int32).to(b.device).contiguous()
-    if b.numel() != G * S * S or p.numel() != G or (gm is not None and gm.numel() != G):
-        raise ValueError("vcf: expected boards [G, S, S] with players (and game) of G entries")
+    b, p, gm, G, S = _board_args("vcf", boards, players, game)
     if actions is not None and (not torch.is_tensor(actions) or actions.dtype != torch.int32
                                 or actions.device != b.device or not actions.is_contiguous()):
         raise ValueError("vcf: actions must be a contiguous int32 tensor on the boards' device (updated in place)")
@@ -993,82 +1012,3 @@ def vcf(boards, players, depth=VCF_DEPTH, nodes=VCF_NODES, game=None, actions=No
                          ptr(mv), _lib.nbytes(mv), ptr(ln), _lib.nbytes(ln), ptr(nd), _lib.nbytes(nd), ptr(actions),
                          _lib.nbytes(actions), _lib.stream_ptr(stream)))
     return st, mv, ln, nd
-
-
-def _has_five(board, n_in_row=5):
-    """Any run of n_in_row equal non-zero stones on an int8 [S,S] board (rows, columns, diagonals)."""
-    S = board.shape[0]
-    for b in (board, board.T):
-        for k in range(S - n_in_row + 1):
-            w = b[:, k:k + n_in_row]
-            if ((w == w[:, :1]).all(axis=1) & (w[:, 0] != 0)).any():
-                return True
-    for b in (board, board[:, ::-1]):
-        for off in range(-(S - n_in_row), S - n_in_row + 1):
-            d = np.diagonal(b, off)
-            for k in range(len(d) - n_in_row + 1):
-                w = d[k:k + n_in_row]
-                if w[0] != 0 and (w == w[0]).all():
-                    return True
-    return False
-
-
-def _place_stones(rs, A, size, n, n_in_row):
-    """n stones of alternating colour (black first) on random cells of an empty board with no n_in_row
-    line, drawn from ``rs`` (redrawn until the board holds no line).  Returns (board int8[A], cells)."""
-    while True:
-        cells = rs.permutation(A)[:n]
-        b = np.zeros(A, np.int8)
-        b[cells[0::2]] = 1
-        b[cells[1::2]] = -1
-        if not _has_five(b.reshape(size, size), n_in_row):
-            return b, cells
-
-
-def seeded_openings(game_ids, size, seed, ks=(0, 4, 8), stagger=0, n_in_row=5):
-    """SURVEY §8(d)'s synthetic starts: game ``gid`` draws from ``RandomState(seed + gid)`` an opening of
-    k in ``ks`` stones (empty boards plus k in {0, 4, 8}) and, with ``stagger`` > 0, uniform(0, stagger)
-    further stones (at most 2A/5 in all), so that the G games are spread over their lifetimes and some finish (and restart
-    from the empty board) in any window of a few moves: the steady state a long self-play run is in.
-    Returns (boards int8 [G,S,S], players int8 [G], last_moves int32 [G], move_counts int32 [G])."""
-    A = size * size
-    G = len(game_ids)
-    boards = np.zeros((G, size, size), np.int8)
-    players = np.ones(G, np.int8)
-    last = np.full(G, -1, np.int32)
-    counts = np.zeros(G, np.int32)
-    for i, gid in enumerate(game_ids):
-        rs = np.random.RandomState((int(seed) + int(gid)) % (2 ** 32))
-        n = int(ks[rs.randint(len(ks))]) + (int(rs.randint(0, stagger + 1)) if stagger > 0 else 0)
-        n = min(n, 2 * A // 5)  # small boards: room left to play, and a line-free draw stays likely
-        b, cells = _place_stones(rs, A, size, n, n_in_row)
-        boards[i] = b.reshape(size, size)
-        players[i] = 1 if n % 2 == 0 else -1
-        last[i] = cells[-1] if n else -1
-        counts[i] = n
-    return boards, players, last, counts
-
-
-def random_openings(G, size, rs, max_stones, n_in_row=5):
-    """Staggered game starts for measurements: game g gets an opening of uniform(0, max_stones) stones of
-    alternating colour (black first) on random cells, with no n_in_row line on the board, the player to
-    move after it and its last stone.  Returns (boards int8 [G,S,S], players int8 [G], last_moves int32 [G],
-    move_counts int32 [G]) for BatchedSelfPlayEngine.set_positions / GameHistory.set_start."""
-    A = size * size
-    boards = np.zeros((G, size, size), np.int8)
-    players = np.ones(G, np.int8)
-    last = np.full(G, -1, np.int32)
-    counts = rs.randint(0, max_stones + 1, G).astype(np.int32)
-    for g in range(G):
-        while True:
-            n = int(counts[g])
-            cells = rs.permutation(A)[:n]
-            b = np.zeros(A, np.int8)
-            b[cells[0::2]] = 1
-            b[cells[1::2]] = -1
-            if not _has_five(b.reshape(size, size), n_in_row):
-                break
-        boards[g] = b.reshape(size, size)
-        players[g] = 1 if n % 2 == 0 else -1
-        last[g] = cells[-1] if n else -1
-    return boards, players, last, counts

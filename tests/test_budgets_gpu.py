@@ -161,6 +161,28 @@ def test_uniform_and_cleared_budgets_equal_an_engine_without_budgets(gmz):
     assert eng.errors() == 0 and plain.errors() == 0
 
 
+def test_four_uploads_in_a_row_leave_the_last_budgets(gmz):
+    """set_budgets four times with four arrays and no host synchronisation in between: the uploads take the two
+    pinned staging buffers in turn, the third and fourth each a buffer used before.  The search that follows equals,
+    bit for bit, that of a fresh engine given only the fourth array."""
+    size, cap, mode, _, _ = CASES["mz9"]
+    G = 8
+    boards, players, lastm, gumbel = (x[4:4 + G] for x in _case("mz9")[:4])
+    arrays = [np.array(a, np.int32) for a in ([50, 1, 16, 17, 33, 2, 49, 50], [1, 50, 2, 40, 7, 31, 32, 15],
+                                              [25, 25, 50, 1, 16, 16, 3, 48], [17, 33, 1, 50, 2, 49, 15, 8])]
+    fresh = _engine(gmz, size, cap, mode, G)
+    fresh.set_budgets(arrays[3])
+    want = _run(fresh, boards, players, lastm, gumbel)
+    eng = _engine(gmz, size, cap, mode, G)
+    for a in arrays:
+        eng.set_budgets(a)
+    assert np.array_equal(eng.budgets, arrays[3])
+    got = _run(eng, boards, players, lastm, gumbel)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+    assert eng.errors() == 0 and fresh.errors() == 0
+
+
 def test_late_game_slots_follow_each_games_budget(gmz):
     """Six moves of search + play from near-full 9x9 boards (3..24 legal moves, games ending and restarting from the
     empty board) with fixed mixed budgets: the hidden-state slots are placed one ply behind from each game's own

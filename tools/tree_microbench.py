@@ -39,7 +39,7 @@ for G in [int(x) for x in a.games.split(",")]:
         check(L.gmz_engine_begin_move(eng.handle, None, eng.seed, ptr(eng.obs), s))
         eng.net.initial(eng.obs, eng.root_slot, eng.logits, eng.value, s)
         check(L.gmz_engine_set_root(eng.handle, ptr(eng.logits), ptr(eng.value), s))
-        eng._sync_status()
+        eng.sync_status()
         waves = eng.waves_needed()
         for _ in range(waves):
             e0, e1, e2, e3 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
