@@ -37,6 +37,7 @@ _SIGS = {
     "gmz_game_winning_scan": ([P, P, P, I, I, I, P, P, P, P], I),
     "gmz_game_anchor_move": ([P, P, P, P, SZ, I, I, I, I, ctypes.c_double, P, SZ, P, SZ, P], I),
     "gmz_game_vcf": ([P, P, P, I, I, I, I, I, P, SZ, P, SZ, P, SZ, P, SZ, P, SZ, P], I),
+    "gmz_game_alphabeta": ([P, P, P, P, SZ, ctypes.c_double, I, I, I, I, I, I, P, SZ, P, SZ, P, SZ, P, SZ, P, SZ, P], I),
     "gmz_engine_create": ([ctypes.POINTER(EngineCfg), ctypes.POINTER(P)], I),
     "gmz_engine_destroy": ([P], I),
     "gmz_engine_game_state": ([P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)], I),

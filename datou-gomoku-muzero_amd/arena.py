@@ -15,14 +15,17 @@ idle slots) and the keyed Gumbel noise (gmz_gumbel_keyed).  DESIGN.md §8b has t
 
 Either side may be an AnchorPlayer instead of a network: a fixed opponent that does not search ("threat": complete a
 five, block one, otherwise build or break lines; "uniform": a random legal move; "vcf": the threat player with a
-forced-win solver in front of it, gmz_game_vcf), whose move is one launch (gmz_game_anchor_move; two for "vcf") on the
-engine's boards.  Anchors stay the same from run to run, so a score against one is an
+forced-win solver in front of it, gmz_game_vcf; "ab": a depth-limited alpha-beta search over the threat rule's scores
+between the two, gmz_game_alphabeta), whose move is one launch (gmz_game_anchor_move; two for "vcf", three for "ab") on
+the engine's boards.  Anchors stay the same from run to run, so a score against one is an
 absolute strength reading.
 
     python -m datou_gomoku_muzero_amd.arena --a CKPT --b CKPT --games N [--precision-a fp16 --precision-b bf16
                                                                          --sims-a 400 --sims-b 200]
     python -m datou_gomoku_muzero_amd.arena --a CKPT --b anchor:threat --games N [--anchor-scale X]
     python -m datou_gomoku_muzero_amd.arena --a CKPT --b anchor:vcf --games N [--anchor-depth 10 --anchor-nodes 2048]
+    python -m datou_gomoku_muzero_amd.arena --a CKPT --b anchor:ab --games N [--anchor-plies 4 --anchor-width 8
+                                                                            --anchor-nodes 2048]
 """
 import argparse
 import json
@@ -171,43 +174,52 @@ class AnchorPlayer:
     """A fixed opponent that does not search a tree (engine.anchor_move), as a side of an Arena.
     ``kind`` "threat": the one-ply threat player; "uniform": a random legal move; "vcf": the forced-win solver's move
     (engine.vcf: at most ``depth`` attacker moves and ``nodes`` nodes per board) where it finds a win by continuous
-    fours, the threat player's move everywhere else.  ``scale`` multiplies the keyed Gumbel noise added to the cell
-    scores (None: 0 for threat and vcf, where the noise only breaks ties, and 1 for uniform)."""
+    fours, the threat player's move everywhere else; "ab": the solver's move where a forced win exists, else the move
+    of the alpha-beta search (engine.alphabeta: ``plies`` deep over the ``width`` best cells of a node, at most ``nodes``
+    nodes per board, the budget of each of the two searches) where that search finished, else the threat player's.
+    ``scale`` multiplies the keyed Gumbel noise added to the cell scores (None: 0 for threat, vcf and ab, where the
+    noise only breaks ties, and 1 for uniform)."""
     kind: str = "threat"
     scale: float = None
     depth: int = 10
     nodes: int = 2048
+    plies: int = 4
+    width: int = 8
 
     def checked(self):
-        """(kind, scale) with the default scale filled in, (kind, scale, depth, nodes) for "vcf"; ValueError for an
-        unknown kind, a scale that is negative or not finite, or, for "vcf", a depth outside [1, 16] or nodes outside
-        [1, 1 << 20]."""
-        if self.kind not in ("threat", "uniform", "vcf"):
-            raise ValueError("AnchorPlayer: kind must be 'threat', 'uniform' or 'vcf', got %r" % (self.kind,))
+        """(kind, scale) with the default scale filled in, (kind, scale, depth, nodes) for "vcf" and (kind, scale,
+        depth, nodes, plies, width) for "ab"; ValueError for an unknown kind, a scale that is negative or not finite,
+        for "vcf" and "ab" a depth outside [1, 16] or nodes outside [1, 1 << 20], or, for "ab", plies outside [1, 8]
+        or a width outside [1, 16]."""
+        if self.kind not in ("threat", "uniform", "vcf", "ab"):
+            raise ValueError("AnchorPlayer: kind must be 'threat', 'uniform', 'vcf' or 'ab', got %r" % (self.kind,))
         scale = (1.0 if self.kind == "uniform" else 0.0) if self.scale is None else float(self.scale)
         if not (scale >= 0.0 and math.isfinite(scale)):
             raise ValueError("AnchorPlayer: scale must be finite and >= 0, got %r" % (self.scale,))
-        if self.kind != "vcf":
+        if self.kind not in ("vcf", "ab"):
             return self.kind, scale
-        for what, v, hi in (("depth", self.depth, 16), ("nodes", self.nodes, 1 << 20)):
+        limits = [("depth", self.depth, 16), ("nodes", self.nodes, 1 << 20)]
+        if self.kind == "ab":
+            limits += [("plies", self.plies, 8), ("width", self.width, 16)]
+        for what, v, hi in limits:
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
                 raise ValueError("AnchorPlayer: %s must be an integer in [1, %d], got %r" % (what, hi, v))
-        return self.kind, scale, int(self.depth), int(self.nodes)
+        return (self.kind, scale) + tuple(int(v) for _, v, _ in limits)
 
     @property
     def name(self):
         return ANCHOR_PREFIX + self.kind
 
 
-def anchor_from_name(name, scale=None, depth=None, nodes=None):
-    """AnchorPlayer of "anchor:threat" / "anchor:uniform" / "anchor:vcf" (``depth`` and ``nodes``: the solver's limits,
-    None = AnchorPlayer's defaults); None for any other string (a checkpoint path)."""
+def anchor_from_name(name, scale=None, depth=None, nodes=None, plies=None, width=None):
+    """AnchorPlayer of "anchor:threat" / "anchor:uniform" / "anchor:vcf" / "anchor:ab" (``depth`` and ``nodes``: the
+    solver's limits, ``plies``, ``width`` and ``nodes``: the alpha-beta search's; None = AnchorPlayer's defaults); None
+    for any other string (a checkpoint path)."""
     if isinstance(name, str) and name.startswith(ANCHOR_PREFIX):
         a = AnchorPlayer(name[len(ANCHOR_PREFIX):], scale)
-        if depth is not None:
-            a.depth = depth
-        if nodes is not None:
-            a.nodes = nodes
+        for what, v in (("depth", depth), ("nodes", nodes), ("plies", plies), ("width", width)):
+            if v is not None:
+                setattr(a, what, v)
         return a
     return None
 
@@ -228,7 +240,8 @@ class Arena:
     ``streams=2``: two engines of num_slots / 2 slots on two HIP streams, offset by one ply so that both sides work
     at every ply; the games are the same ones.  ``sims=(n_a, n_b)``: a simulation budget per network (ignored for
     an anchor side).  On an anchor's ply an engine runs the keyed noise, the anchor's launch (for "vcf" the threat
-    launch, then the solver's over the same actions) and play_refill, and no search."""
+    launch, then the solver's over the same actions; for "ab" the alpha-beta launch between the two) and play_refill,
+    and no search."""
 
     def __init__(self, cfg, net_a, net_b, num_slots, openings, seed=0, record_moves=False, streams=None,
                  device="cuda", sims=None, **overrides):
@@ -328,9 +341,14 @@ class Arena:
                 e.keyed_gumbel(self.gumbel[i], self.streams[i])
                 if self.anchors[k] is not None:
                     kind, scale = self.anchors[k][:2]
-                    if kind == "vcf":  # the threat rule's move, then the solver's over it where it found a win
+                    if kind in ("vcf", "ab"):
+                        # the threat rule's move, the alpha-beta move over it where that search finished ("ab"), then
+                        # the solver's over both where it found a win
+                        depth, nodes = self.anchors[k][2:4]
                         e.anchor_move(self.gumbel[i], "threat", scale, self.streams[i])
-                        actions[i] = e.vcf_move(*self.anchors[k][2:], stream=self.streams[i])
+                        if kind == "ab":
+                            e.ab_move(self.gumbel[i], scale, *self.anchors[k][4:], nodes=nodes, stream=self.streams[i])
+                        actions[i] = e.vcf_move(depth, nodes, stream=self.streams[i])
                     else:
                         actions[i] = e.anchor_move(self.gumbel[i], kind, scale, self.streams[i])
                     continue
@@ -395,14 +413,16 @@ def blocks_of(state_dict):
 
 def play_match(sd_a, sd_b, cfg, games, num_slots=None, precision_a="fp16", precision_b="fp16", seed=0,
                stones=(2, 4, 6), record_moves=False, streams=None, device="cuda", sims=None, anchor_scale=None,
-               anchor_depth=None, anchor_nodes=None):
+               anchor_depth=None, anchor_nodes=None, anchor_plies=None, anchor_width=None):
     """A match of ``games`` games (rounded up to an even number: games / 2 openings from paired_openings) between
     the networks of two state dicts, which may differ in depth and precision.  Either side may instead be an
-    AnchorPlayer or its name ("anchor:threat", "anchor:uniform", "anchor:vcf", with ``anchor_scale`` and, for the
-    solver, ``anchor_depth`` and ``anchor_nodes``).  Returns a MatchResult."""
+    AnchorPlayer or its name ("anchor:threat", "anchor:uniform", "anchor:vcf", "anchor:ab", with ``anchor_scale``, for
+    the solver ``anchor_depth`` and ``anchor_nodes`` and for the alpha-beta search ``anchor_plies``, ``anchor_width``
+    and ``anchor_nodes``).  Returns a MatchResult."""
     from . import engine as E, network as N
     from .config import from_any
-    sides = [anchor_from_name(sd, anchor_scale, anchor_depth, anchor_nodes) or sd for sd in (sd_a, sd_b)]
+    sides = [anchor_from_name(sd, anchor_scale, anchor_depth, anchor_nodes, anchor_plies, anchor_width) or sd
+             for sd in (sd_a, sd_b)]
     c = from_any(cfg)
     if sims is not None:
         searching = [n for n, sd in zip(sims, sides) if not isinstance(sd, AnchorPlayer)]
@@ -451,15 +471,20 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m datou_gomoku_muzero_amd.arena", description="A match between two network checkpoints on the GPU: paired openings, "
                                              "wins / draws / losses and the Elo difference as one JSON line.")
     ap.add_argument("--a", required=True, help="checkpoint of network A (RecordStore .db or torch.save file), or "
-                                               "anchor:threat / anchor:uniform / anchor:vcf for a fixed opponent")
+                                               "anchor:threat / anchor:uniform / anchor:vcf / anchor:ab for a fixed opponent")
     ap.add_argument("--b", required=True,
-                    help="checkpoint of network B, or anchor:threat / anchor:uniform / anchor:vcf")
+                    help="checkpoint of network B, or anchor:threat / anchor:uniform / anchor:vcf / anchor:ab")
     ap.add_argument("--anchor-scale", type=float, default=None,
-                    help="noise scale of an anchor side (default: 0 for threat and vcf, 1 for uniform)")
+                    help="noise scale of an anchor side (default: 0 for threat, vcf and ab, 1 for uniform)")
     ap.add_argument("--anchor-depth", type=int, default=None,
-                    help="attacker moves the anchor:vcf solver looks ahead (default 10, at most 16)")
+                    help="attacker moves the solver of anchor:vcf and anchor:ab looks ahead (default 10, at most 16)")
     ap.add_argument("--anchor-nodes", type=int, default=None,
-                    help="node budget per board of the anchor:vcf solver (default 2048)")
+                    help="node budget per board of the anchor:vcf solver and of each of anchor:ab's two searches "
+                         "(default 2048)")
+    ap.add_argument("--anchor-plies", type=int, default=None,
+                    help="plies the anchor:ab search looks ahead (default 4, at most 8)")
+    ap.add_argument("--anchor-width", type=int, default=None,
+                    help="candidate cells per node of the anchor:ab search (default 8, at most 16)")
     ap.add_argument("--games", type=int, required=True)
     ap.add_argument("--precision-a", default="fp16", choices=("fp16", "bf16"))
     ap.add_argument("--precision-b", default="fp16", choices=("fp16", "bf16"))
@@ -475,8 +500,8 @@ def main(argv=None):
     from .config import GmzConfig
     cfg = GmzConfig(BOARD_SIZE=a.board_size, NUM_SIMULATIONS=a.sims, MCTS_IMPLEMENTATION=a.mode)
     sims = (a.sims_a or a.sims, a.sims_b or a.sims)
-    sides = [anchor_from_name(x, a.anchor_scale, a.anchor_depth, a.anchor_nodes) or load_checkpoint(x)
-             for x in (a.a, a.b)]
+    sides = [anchor_from_name(x, a.anchor_scale, a.anchor_depth, a.anchor_nodes, a.anchor_plies, a.anchor_width)
+             or load_checkpoint(x) for x in (a.a, a.b)]
     res = play_match(sides[0], sides[1], cfg, a.games, a.slots or None, a.precision_a, a.precision_b, a.seed,
                      streams=a.streams, sims=sims)
     out = res.as_dict()

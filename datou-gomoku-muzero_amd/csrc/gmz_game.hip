@@ -582,6 +582,333 @@ GMZ_EXPORT int gmz_game_vcf(const int8_t *boards, const int8_t *players, const i
   return 0;
 }
 
+namespace gmz {
+
+constexpr int AB_MAX_PLIES = 8, AB_MAX_WIDTH = 16, AB_MAX_NODES = 1 << 20, AB_MAX_N = 8;
+constexpr int64_t AB_WIN = 1ll << 40, AB_INF = 1ll << 50;
+// log2 of W_own[m] and of W_opp[m] (m = 0..4, five bits each); W_opp[4] is 0 and is left out by the caller
+constexpr uint32_t AB_OWN_SHIFTS = 26u | 13u << 5 | 6u << 10 | 2u << 15 | 0u << 20;
+constexpr uint32_t AB_OPP_SHIFTS = 20u | 10u << 5 | 5u << 10 | 1u << 15;
+
+// The threat rule's score (k_anchor_move's) of the empty cell (r0, c0) for the side whose stones are
+// lines[so], read from the bit lines as vcf_cell reads them: per direction a shifted piece of two line words, each
+// window a run of n bits whose stones are two popcounts.
+__device__ __forceinline__ int64_t ab_score(const uint32_t (*lines)[4][VCF_LINES], int size, int n, int r0, int c0,
+                                            int so) {
+  const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+  const uint32_t run = (1u << n) - 1;
+  int64_t sc = 0;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    int back = n - 1, fwd = n - 1;
+    if (dr[d]) {
+      back = min(back, r0);
+      fwd = min(fwd, size - 1 - r0);
+    }
+    if (dc[d] > 0) {
+      back = min(back, c0);
+      fwd = min(fwd, size - 1 - c0);
+    } else if (dc[d] < 0) {
+      back = min(back, size - 1 - c0);
+      fwd = min(fwd, c0);
+    }
+    if (back + fwd < n - 1) continue;  // no window through the cell lies on the board
+    int line, pos;
+    vcf_line(d, r0, c0, size, line, pos);
+    const uint32_t span = (2u << (back + fwd)) - 1;  // back + fwd + 1 <= size bits
+    const uint32_t own = (lines[so][d][line] >> (pos - back)) & span;
+    const uint32_t opp = (lines[so ^ 1][d][line] >> (pos - back)) & span;
+    for (int w = 0; w <= back + fwd - (n - 1); ++w) {  // the window of bits [w, w + n)
+      const uint32_t wm = run << w;
+      const int n_own = __popc(own & wm), n_opp = __popc(opp & wm);
+      if (n_opp == 0) sc += 1ll << ((AB_OWN_SHIFTS >> (5 * min(n - 1 - n_own, 4))) & 31);
+      if (n_own == 0 && n - 1 - n_opp < 4) sc += 1ll << ((AB_OPP_SHIFTS >> (5 * (n - 1 - n_opp))) & 31);
+    }
+  }
+  return sc;
+}
+
+// The depth-limited alpha-beta anchor of DESIGN.md §8b for G boards, shaped like k_vcf: one wave per board, a workgroup
+// of one wave, the board as k_vcf's bit lines in LDS, lane l owning the cells l, l + 64, ... (up to 8).  The search is
+// serial and wave-uniform (every branch is taken on a value all lanes hold: a wave reduction made uniform, or a word
+// all lanes read from LDS); a node's work is wide.  Every node takes one pass over the windows (lane l: the windows
+// that start on its cells, four per cell), which gives five(b, s) by its smallest cell and the static value E(b, s);
+// a node that goes on scores its empty cells (ab_score) and picks the ``width`` best with one wave butterfly each over
+// the 64-bit key score << 9 | 511 - cell (the root: over (key, noise, -cell) with the double key of k_anchor_move).
+// Nothing is kept from node to node but the board and, per level, alpha, beta, best and the candidates, all in LDS:
+// an explicit stack, no recursion, no scratch, no global memory but the inputs and outputs, and no atomics but the
+// LDS ORs that build the bit lines.  Each turn of the outer loop counts a node, so max_nodes bounds the launch.
+__global__ void __launch_bounds__(WAVE) k_alphabeta(const int8_t *__restrict__ boards, const int8_t *__restrict__ players,
+                                                    const int32_t *__restrict__ game, const double *__restrict__ noise,
+                                                    double scale, int size, int n, int plies, int width, int max_nodes,
+                                                    int8_t *__restrict__ status, int32_t *__restrict__ moves,
+                                                    int64_t *__restrict__ values, int32_t *__restrict__ nodes,
+                                                    int32_t *__restrict__ actions) {
+  __shared__ uint32_t lines[2][4][VCF_LINES];  // [0]: the stones of p, [1]: of -p
+  __shared__ uint16_t rc[MAX_A];               // a cell's row << 8 | column
+  __shared__ int64_t s_alpha[AB_MAX_PLIES], s_beta[AB_MAX_PLIES], s_best[AB_MAX_PLIES];
+  __shared__ int16_t s_cand[AB_MAX_PLIES][AB_MAX_WIDTH];
+  __shared__ int32_t s_count[AB_MAX_PLIES], s_next[AB_MAX_PLIES];  // candidates of the level, and how many were played
+  const int g = blockIdx.x, A = size * size, lane = threadIdx.x;
+  const int nj = (A + WAVE - 1) / WAVE;
+  for (int i = lane; i < 2 * 4 * VCF_LINES; i += WAVE) (&lines[0][0][0])[i] = 0;
+  __syncthreads();
+  const bool idle = game && game[g] < 0;  // an idle arena slot
+  const int p = players[g];
+  const int8_t *src = boards + (size_t)g * A;
+  int stones = 0;
+  if (!idle)
+    for (int j = 0; j < nj; ++j) {
+      const int i = j * WAVE + lane, v = i < A ? src[i] : 0;
+      stones += __popcll(__ballot(v != 0));
+      if (i < A) {
+        const int r = i / size, c = i - r * size;
+        rc[i] = (uint16_t)(r << 8 | c);
+        if (v != 0)
+          for (int d = 0; d < 4; ++d) {
+            int line, pos;
+            vcf_line(d, r, c, size, line, pos);
+            atomicOr(&lines[v == p ? 0 : 1][d][line], 1u << pos);
+          }
+      }
+    }
+  if (idle || stones == A) {  // skipped: actions[g] stays as it is
+    if (lane == 0) {
+      status[g] = 3;
+      moves[g] = -1;
+      if (values) values[g] = 0;
+      if (nodes) nodes[g] = 0;
+    }
+    return;
+  }
+  __syncthreads();
+  const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+  const uint32_t run = (1u << n) - 1;
+  // a stone of side so goes on or off cell c: lane d flips its bit in orientation d
+  auto flip = [&](int c, int so) {
+    if (lane < 4) {
+      const int x = rc[c];
+      int line, pos;
+      vcf_line(lane, x >> 8, x & 255, size, line, pos);
+      lines[so][lane][line] ^= 1u << pos;
+    }
+  };
+  int level = 0, count = 0, st = 0, mv = -1;
+  int64_t val = 0, alpha = -AB_INF, beta = AB_INF;
+  for (;;) {  // value() of the node at ``level`` (= ply; plies - level plies left), side level & 1 to move
+    if (++count > max_nodes) {  // 1.
+      st = 2;
+      break;
+    }
+    const int so = level & 1;
+    bool ends = true;
+    int64_t v = 0;
+    if (stones + level < A) {  // 2. (else: no empty cell, 0)
+      // 3. and 4.: every window by its first cell
+      int64_t e = 0;
+      int fmin = MAX_A;
+#pragma unroll 1
+      for (int cell = lane; cell < A; cell += WAVE) {
+        const int r = rc[cell] >> 8, c = rc[cell] & 255;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          const int re = r + (n - 1) * dr[d], ce = c + (n - 1) * dc[d];
+          if (re >= size || ce < 0 || ce >= size) continue;
+          int line, pos;
+          vcf_line(d, r, c, size, line, pos);
+          const uint32_t own = (lines[so][d][line] >> pos) & run, opp = (lines[so ^ 1][d][line] >> pos) & run;
+          const int n_own = __popc(own), n_opp = __popc(opp);
+          if (n_opp == 0 && n_own > 0) {
+            e += 2ll << (3 * (n_own - 1));
+            if (n_own == n - 1) fmin = min(fmin, cell + __builtin_ctz(~own & run) * (dr[d] * size + dc[d]));
+          } else if (n_own == 0 && n_opp > 0) {
+            e -= 1ll << (3 * (n_opp - 1));
+          }
+        }
+      }
+      for (int off = WAVE / 2; off > 0; off >>= 1) {
+        e += __shfl_xor(e, off);
+        fmin = min(fmin, __shfl_xor(fmin, off));
+      }
+      fmin = __builtin_amdgcn_readfirstlane(fmin);
+      if (fmin < MAX_A) {  // 3. the mover completes a five
+        if (level == 0) {
+          mv = fmin;
+          val = AB_WIN;
+          break;
+        }
+        v = AB_WIN - level;
+      } else if (level == plies) {  // 4.
+        v = (int64_t)vcf_uniform((uint64_t)e);
+      } else {
+        ends = false;
+      }
+    }
+    if (!ends) {
+      // 5. and the candidates of 6.
+      int nc = 0;
+      if (level == 0) {  // the anchor rule's order: (key, noise, -cell), key = (double)score + scale * noise
+        double key[NJ], nz[NJ];
+        uint32_t have = 0;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int cell = j * WAVE + lane;
+          key[j] = nz[j] = 0.0;
+          if (j < nj && cell < A) {
+            const int r = rc[cell] >> 8, c = rc[cell] & 255;
+            if (vcf_empty(lines, r, c)) {
+              nz[j] = noise ? noise[(size_t)g * A + cell] : 0.0;
+              key[j] = (double)ab_score(lines, size, n, r, c, so) + scale * nz[j];
+              have |= 1u << j;
+            }
+          }
+        }
+        for (; nc < width; ++nc) {
+          AnchorBest best = {0.0, 0.0, -1};
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            const AnchorBest o = {key[j], nz[j], (have >> j) & 1 ? j * WAVE + lane : -1};
+            if (anchor_better(o, best)) best = o;
+          }
+          for (int off = WAVE / 2; off > 0; off >>= 1) {
+            AnchorBest o;
+            o.key = __shfl_xor(best.key, off);
+            o.noise = __shfl_xor(best.noise, off);
+            o.cell = __shfl_xor(best.cell, off);
+            if (anchor_better(o, best)) best = o;
+          }
+          const int c = __builtin_amdgcn_readfirstlane(best.cell);
+          if (c < 0) break;
+          if ((c & (WAVE - 1)) == lane) have &= ~(1u << (c >> 6));
+          if (lane == 0) s_cand[0][nc] = (int16_t)c;
+        }
+      } else {  // (score, -cell) as one word; 0: no cell (511 - cell > 0 for every cell)
+        uint64_t key[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int cell = j * WAVE + lane;
+          key[j] = 0;
+          if (j < nj && cell < A) {
+            const int r = rc[cell] >> 8, c = rc[cell] & 255;
+            if (vcf_empty(lines, r, c))
+              key[j] = (uint64_t)ab_score(lines, size, n, r, c, so) << 9 | (uint64_t)(MAX_A - 1 - cell);
+          }
+        }
+        for (; nc < width; ++nc) {
+          uint64_t best = 0;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) best = key[j] > best ? key[j] : best;
+          for (int off = WAVE / 2; off > 0; off >>= 1) {
+            const uint64_t o = __shfl_xor((unsigned long long)best, off);
+            best = o > best ? o : best;
+          }
+          best = vcf_uniform(best);
+          if (best == 0) break;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            if (key[j] == best) key[j] = 0;
+          if (lane == 0) s_cand[level][nc] = (int16_t)(MAX_A - 1 - (int)(best & (MAX_A - 1)));
+        }
+      }
+      if (lane == 0) {
+        s_alpha[level] = alpha;
+        s_beta[level] = beta;
+        s_best[level] = -AB_INF;
+        s_count[level] = nc;
+        s_next[level] = 0;
+      }
+      __syncthreads();
+    } else {
+      // 7. the value goes up, through every level that has no candidate left or is cut off (level >= 1 here: the
+      // root has an empty cell, no five and plies >= 1)
+      bool done = false;
+      for (;;) {
+        --level;
+        const int next = __builtin_amdgcn_readfirstlane(s_next[level]);
+        const int nc = __builtin_amdgcn_readfirstlane(s_count[level]);
+        const int c = __builtin_amdgcn_readfirstlane((int)s_cand[level][next - 1]);
+        flip(c, level & 1);
+        v = -v;
+        int64_t a = (int64_t)vcf_uniform((uint64_t)s_alpha[level]), best = (int64_t)vcf_uniform((uint64_t)s_best[level]);
+        const int64_t b = (int64_t)vcf_uniform((uint64_t)s_beta[level]);
+        if (v > best) {
+          best = v;
+          if (level == 0) mv = c;
+        }
+        if (v > a) a = v;
+        __syncthreads();
+        if (lane == 0) {
+          s_best[level] = best;
+          s_alpha[level] = a;
+        }
+        __syncthreads();
+        if (a < b && next < nc) break;  // 6. the next candidate of this level
+        if (level == 0) {
+          val = best;
+          done = true;
+          break;
+        }
+        v = best;
+      }
+      if (done) break;
+    }
+    // 6. the next candidate of ``level`` goes on the board
+    const int next = __builtin_amdgcn_readfirstlane(s_next[level]);
+    const int c = __builtin_amdgcn_readfirstlane((int)s_cand[level][next]);
+    alpha = -(int64_t)vcf_uniform((uint64_t)s_beta[level]);
+    beta = -(int64_t)vcf_uniform((uint64_t)s_alpha[level]);
+    __syncthreads();
+    if (lane == 0) s_next[level] = next + 1;
+    flip(c, level & 1);
+    ++level;
+    __syncthreads();
+  }
+  if (lane == 0) {
+    status[g] = (int8_t)st;
+    moves[g] = st == 0 ? mv : -1;
+    if (values) values[g] = st == 0 ? val : 0;
+    if (nodes) nodes[g] = count;
+    if (actions && st == 0) actions[g] = mv;
+  }
+}
+
+}  // namespace gmz
+
+GMZ_EXPORT int gmz_game_alphabeta(const int8_t *boards, const int8_t *players, const int32_t *game, const double *noise,
+                                  size_t noise_bytes, double scale, int G, int size, int n_in_row, int plies, int width,
+                                  int max_nodes, int8_t *status, size_t status_bytes, int32_t *moves, size_t moves_bytes,
+                                  int64_t *values, size_t values_bytes, int32_t *nodes, size_t nodes_bytes,
+                                  int32_t *actions, size_t actions_bytes, void *stream) {
+  if (G <= 0) return fail("gmz_game_alphabeta: bad shape: G must be >= 1");
+  if (size <= 0 || size * size > MAX_A)
+    return fail("gmz_game_alphabeta: bad shape: size must be >= 1 and size * size <= 512");
+  if (n_in_row < 3 || n_in_row > size || n_in_row > AB_MAX_N)
+    return fail("gmz_game_alphabeta: n_in_row must be in [3, min(size, 8)]");
+  if (plies < 1 || plies > AB_MAX_PLIES) return fail("gmz_game_alphabeta: plies must be in [1, 8]");
+  if (width < 1 || width > AB_MAX_WIDTH) return fail("gmz_game_alphabeta: width must be in [1, 16]");
+  if (max_nodes < 1 || max_nodes > AB_MAX_NODES) return fail("gmz_game_alphabeta: max_nodes must be in [1, 1048576]");
+  if (!(scale >= 0.0) || !std::isfinite(scale)) return fail("gmz_game_alphabeta: scale must be finite and >= 0");
+  if (!boards || !players || !status || !moves)
+    return fail(std::string("gmz_game_alphabeta: null ") +
+                (!boards ? "boards" : !players ? "players" : !status ? "status" : "moves"));
+  const size_t A = (size_t)size * size;
+  const struct {
+    const char *name, *unit;
+    const void *p;
+    size_t have, each;
+  } bufs[6] = {{"noise", "G * A * 8", noise, noise_bytes, A * 8}, {"status", "G * 1", status, status_bytes, 1},
+               {"moves", "G * 4", moves, moves_bytes, 4},         {"values", "G * 8", values, values_bytes, 8},
+               {"nodes", "G * 4", nodes, nodes_bytes, 4},         {"actions", "G * 4", actions, actions_bytes, 4}};
+  for (const auto &x : bufs)
+    if (x.p && x.have < (size_t)G * x.each)
+      return fail(std::string("gmz_game_alphabeta: ") + x.name + " holds " + std::to_string(x.have) + " bytes, " +
+                  x.unit + " = " + std::to_string((size_t)G * x.each));
+  hipLaunchKernelGGL(k_alphabeta, dim3(G), dim3(WAVE), 0, (hipStream_t)stream, boards, players, game, noise, scale, size,
+                     n_in_row, plies, width, max_nodes, status, moves, values, nodes, actions);
+  GMZ_LAUNCH_CHECK();
+  return 0;
+}
+
 GMZ_EXPORT int gmz_game_check_win(const int8_t *boards, int G, int size, int n_in_row, const int32_t *moves,
                                   uint8_t *out, void *stream) {
   if (G <= 0 || size <= 0 || size * size > MAX_A) return fail("gmz_game_check_win: bad shape");

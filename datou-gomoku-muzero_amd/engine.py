@@ -164,6 +164,7 @@ class BatchedSelfPlayEngine:
         self._refill_pending = False
         self._state_ptrs = None  # device pointers of the engine-owned game state (anchor_move, vcf_move)
         self.vcf_status = self.vcf_moves = None  # the last vcf_move launch's statuses and moves (made at the first)
+        self.ab_status = self.ab_moves = None  # the same of ab_move
         self.finished_seen = 0  # the match's finished-games counter as of the last status read (play_refill)
         self.moves_played = 0   # moves counted from the statuses read after play_refill calls
         self._hb_net = None     # the backend whose pool the last placement was checked against
@@ -599,6 +600,27 @@ class BatchedSelfPlayEngine:
             None, 0, None, 0, ptr(self.action), _lib.nbytes(self.action), self._stream(stream)))
         return self.action
 
+    def ab_move(self, noise=None, scale=0.0, plies=None, width=None, nodes=None, stream=None):
+        """The alpha-beta anchor (gmz_game_alphabeta, see ``alphabeta``) for the side to move on the engine's own
+        device boards, in one launch on ``stream`` with no host wait: where the search finished its move replaces the
+        entry of ``self.action`` (after anchor_move: the threat rule's move), every other entry stays.  ``noise``:
+        f64[G,A] on the device (keyed_gumbel's) or None.  Returns ``self.action``; the statuses and moves of the
+        launch stay in ``self.ab_status`` / ``self.ab_moves``."""
+        if noise is not None and (not torch.is_tensor(noise) or noise.dtype != torch.float64
+                                  or noise.device.type != self.device.type or not noise.is_contiguous()):
+            raise ValueError("ab_move: noise must be a contiguous float64 tensor on %s" % self.device)
+        if self.ab_status is None:
+            self.ab_status = torch.zeros(self.G, dtype=torch.int8, device=self.device)
+            self.ab_moves = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
+        boards, players, game = self._game_ptrs()
+        check(self.lib.gmz_game_alphabeta(
+            boards, players, game, ptr(noise), _lib.nbytes(noise), float(scale), self.G, self.size, self.cfg.N_IN_ROW,
+            AB_PLIES if plies is None else int(plies), AB_WIDTH if width is None else int(width),
+            AB_NODES if nodes is None else int(nodes), ptr(self.ab_status), _lib.nbytes(self.ab_status),
+            ptr(self.ab_moves), _lib.nbytes(self.ab_moves), None, 0, None, 0, ptr(self.action),
+            _lib.nbytes(self.action), self._stream(stream)))
+        return self.action
+
     def winning_scan(self, boards, players, action=None, counters=None, stream=None):
         """workers.py:49-123 find_winning_moves_rebuilt on the device for G positions (see
         ``winning_scan``); ``counters`` = (missed_fives, missed_totals) int32[G] accumulated in place."""
@@ -1012,3 +1034,35 @@ def vcf(boards, players, depth=VCF_DEPTH, nodes=VCF_NODES, game=None, actions=No
                          ptr(mv), _lib.nbytes(mv), ptr(ln), _lib.nbytes(ln), ptr(nd), _lib.nbytes(nd), ptr(actions),
                          _lib.nbytes(actions), _lib.stream_ptr(stream)))
     return st, mv, ln, nd
+
+
+AB_PLIES, AB_WIDTH, AB_NODES = 4, 8, 2048  # the alpha-beta anchor's defaults
+
+
+def alphabeta(boards, players, plies=AB_PLIES, width=AB_WIDTH, nodes=AB_NODES, noise=None, scale=0.0, game=None,
+              actions=None, stream=None, n_in_row=5):
+    """The depth-limited alpha-beta anchor on G boards (``gmz_game_alphabeta``; the rule: DESIGN.md §8b): a fixed
+    negamax search ``plies`` deep over the ``width`` best cells of the threat rule's scores at every node, at most
+    ``nodes`` nodes per board, in one launch.
+
+    boards int8[G,S,S] and players int8[G] on the device; ``noise`` f64[G,S*S] or None (= 0) and ``scale`` order the
+    root's candidates as ``anchor_move`` orders its cells.  ``game`` int32[G]: a negative entry skips that board.
+    ``actions`` int32[G] on the device is updated in place: entry g becomes the move where the search finished and
+    stays as it is everywhere else.  Returns (status int8[G]: 0 searched, 2 node budget used up, 3 skipped or a full
+    board; move int32[G], -1 unless status is 0; value int64[G], the root's value from the mover's side; nodes
+    int32[G])."""
+    L = _lib.load()
+    b, p, gm, G, S = _board_args("alphabeta", boards, players, game)
+    if actions is not None and (not torch.is_tensor(actions) or actions.dtype != torch.int32
+                                or actions.device != b.device or not actions.is_contiguous()):
+        raise ValueError("alphabeta: actions must be a contiguous int32 tensor on the boards' device (updated in "
+                         "place)")
+    nz = None if noise is None else torch.as_tensor(noise, dtype=torch.float64).to(b.device).contiguous()
+    st = torch.empty(G, dtype=torch.int8, device=b.device)
+    mv, nd = (torch.empty(G, dtype=torch.int32, device=b.device) for _ in range(2))
+    val = torch.empty(G, dtype=torch.int64, device=b.device)
+    check(L.gmz_game_alphabeta(ptr(b), ptr(p), ptr(gm), ptr(nz), _lib.nbytes(nz), float(scale), G, S, int(n_in_row),
+                               int(plies), int(width), int(nodes), ptr(st), _lib.nbytes(st), ptr(mv), _lib.nbytes(mv),
+                               ptr(val), _lib.nbytes(val), ptr(nd), _lib.nbytes(nd), ptr(actions),
+                               _lib.nbytes(actions), _lib.stream_ptr(stream)))
+    return st, mv, val, nd

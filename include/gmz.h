@@ -296,6 +296,38 @@ int gmz_game_vcf(const int8_t *boards_dev, const int8_t *players_dev, const int3
                  int32_t *moves_dev, size_t moves_bytes, int32_t *lengths_dev, size_t lengths_bytes, int32_t *nodes_dev,
                  size_t nodes_bytes, int32_t *actions_dev, size_t actions_bytes, void *stream);
 
+/* A fixed, depth-limited alpha-beta search over the anchor rule's cell scores for the player to move (p =
+ * players_dev[g]) on G boards, in one launch (additive, ABI stays 10).  Every quantity is an integer.
+ * Windows, directions and five(b, s) are gmz_game_vcf's; score(b, s, c) is gmz_game_anchor_move's int64 score of the
+ * empty cell c with s to move; n = n_in_row; WIN = 2^40.
+ *   E(b, s): over every window wholly on the board, one with k >= 1 stones of s and none of -s adds 2 * 8^(k-1), one
+ *     with k >= 1 stones of -s and none of s subtracts 8^(k-1).
+ *   cand(b, s): the width empty cells with the largest (score, -cell) (score descending, ties to the smaller cell;
+ *     fewer when fewer cells are empty).
+ *   value(b, s, d, alpha, beta, ply), from s's side, in this order: (1) nodes += 1, and nodes > max_nodes stops the
+ *     whole search with status 2; (2) no empty cell: 0; (3) five(b, s) not empty: WIN - ply; (4) d == 0: E(b, s);
+ *     (5) best = -2^50; (6) for each c of cand(b, s) in order, with s on c: v = -value(b', -s, d - 1, -beta, -alpha,
+ *     ply + 1); v > best: best = v; v > alpha: alpha = v; alpha >= beta: the loop stops; (7) best.
+ *   The root is value(b, p, plies, -2^50, 2^50, 0) with two differences: a root with five(b, p) not empty answers with
+ *     its smallest cell and the value WIN; and the root's candidates are the width best empty cells in
+ *     gmz_game_anchor_move's order (key, noise, -cell), key = (double)score + scale * noise[c] (noise_dev f64[G][A] or
+ *     NULL = 0; below the root there is no noise).  The root's move is the first candidate whose value is strictly
+ *     larger than all before it.
+ * status_dev int8[G]: 0 searched, 2 node budget used up, 3 skipped (game_dev[g] < 0, game_dev int32[G] or NULL as in
+ * gmz_game_vcf; or a full board).  moves_dev int32[G]: -1 unless status is 0.  values_dev (nullable) int64[G]: the
+ * root's value, 0 unless status is 0.  nodes_dev (nullable) int32[G]: the calls of value (max_nodes + 1 with status 2,
+ * 0 with status 3).  actions_dev (nullable, in/out) int32[G]: entry g becomes the move where status is 0 and is left
+ * alone everywhere else.  Refused before any launch, with nothing written: G < 1, size < 1 or size^2 > 512, n_in_row
+ * outside [3, min(size, 8)], plies outside [1, 8], width outside [1, 16], max_nodes outside [1, 1 << 20], scale
+ * negative or not finite, null boards, players, status or moves, noise_bytes < G * A * 8, status_bytes < G,
+ * moves_bytes / nodes_bytes / actions_bytes < G * 4, values_bytes < G * 8 (each nullable array only with its
+ * pointer).  Stream-ordered; never synchronises. */
+int gmz_game_alphabeta(const int8_t *boards_dev, const int8_t *players_dev, const int32_t *game_dev,
+                       const double *noise_dev, size_t noise_bytes, double scale, int G, int size, int n_in_row,
+                       int plies, int width, int max_nodes, int8_t *status_dev, size_t status_bytes, int32_t *moves_dev,
+                       size_t moves_bytes, int64_t *values_dev, size_t values_bytes, int32_t *nodes_dev,
+                       size_t nodes_bytes, int32_t *actions_dev, size_t actions_bytes, void *stream);
+
 /* ------------------------------------------------------------------ HashNet test network */
 /* Deterministic integer-hash network (definition: oracle/hashnet.py) used for tree parity.
  * Hidden state = uint32 id per slot in hid_pool_dev[G*slots].

@@ -4,8 +4,10 @@ beside ``python bench.py``'s self-play headline on the same GPU (profiles/arena.
 
   python tools/arena_bench.py [--streams 1,2 --steps 10 --warmup 3 --rounds 2] [--b anchor:threat]
   python tools/arena_bench.py --b anchor:vcf [--anchor-depth 10 --anchor-nodes 2048]
+  python tools/arena_bench.py --b anchor:threat,anchor:ab [--anchor-plies 4 --anchor-width 8]   (alternated)
   python tools/arena_bench.py --anchor-launch 200      (the anchor launch alone, by event timing)
   python tools/arena_bench.py --vcf-launch 50          (the solver launch alone, on positions of threat-anchor games)
+  python tools/arena_bench.py --ab-launch 20           (the alpha-beta launch alone, on the same positions)
 
 The book holds more openings than the timed plies can finish, so no slot idles; a move is counted from the
 statuses (arena's ``moves_played``).  Prints one JSON line per (round, streams)."""
@@ -24,8 +26,9 @@ from datou_gomoku_muzero_amd import arena as AR, engine as E, network as N, weig
 from datou_gomoku_muzero_amd.config import GmzConfig  # noqa: E402
 
 
-def measure(cfg, sd, slots, streams, steps, warmup, precision, seed, side_b="self", depth=None, nodes=None):
-    anchor = AR.anchor_from_name(side_b, depth=depth, nodes=nodes)
+def measure(cfg, sd, slots, streams, steps, warmup, precision, seed, side_b="self", depth=None, nodes=None, plies=None,
+            width=None):
+    anchor = AR.anchor_from_name(side_b, depth=depth, nodes=nodes, plies=plies, width=width)
     nets = [N.GomokuNetHip(sd, cfg, num_slots=E.hidden_slots(cfg, slots), max_rows=slots, precision=precision)
             for _ in range(1 if anchor else 2)]
     # 8 games per slot: against the threat anchor a game lasts some 8 plies, so the default 13 plies finish fewer
@@ -72,10 +75,9 @@ def anchor_launch(size, boards, reps, seed):
     return out
 
 
-def vcf_launch(size, boards, reps, seed, depth, nodes, scale=3e3):
-    """Microseconds per gmz_game_vcf launch on ``boards`` positions taken from games between two threat anchors
-    (noise scale 3e3, from the empty board, played by the numpy model tests/vcf_ref.py), by HIP events over ``reps``
-    launches; and the same launch on the slowest board alone, which bounds what one wave holds."""
+def threat_positions(size, boards, seed, scale=3e3):
+    """``boards`` positions taken from games between two threat anchors (noise ``scale``, from the empty board, played
+    by the numpy model tests/vcf_ref.py), on the device: (boards int8 [boards, size, size], players int8 [boards])."""
     import numpy as np
     sys.path.insert(0, os.path.join(REPO, "tests"))
     import vcf_ref  # the numpy model: its games are the positions (tests/test_vcf_gpu.py uses the same)
@@ -84,7 +86,46 @@ def vcf_launch(size, boards, reps, seed, depth, nodes, scale=3e3):
         games += max(boards // 32, 1)
         bb, pp = vcf_ref.threat_game_positions(size, 5, games, seed, scale)
     b = torch.from_numpy(bb[:boards].reshape(boards, size, size).copy()).cuda()
-    p = torch.from_numpy(pp[:boards].copy()).cuda()
+    return b, torch.from_numpy(pp[:boards].copy()).cuda()
+
+
+def ab_launch(size, boards, reps, seed, plies, width, nodes):
+    """Microseconds per gmz_game_alphabeta launch on the positions of threat_positions, by HIP events over ``reps``
+    launches; the same launch on the slowest board alone; and the node counts, whose largest bounds the launch."""
+    import numpy as np
+    b, p = threat_positions(size, boards, seed)
+    out = dict(size=size, boards=boards, reps=reps, plies=plies, width=width, nodes=nodes)
+
+    def timed(bb, pp, n):
+        for _ in range(2):
+            E.alphabeta(bb, pp, plies, width, nodes)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(n):
+            E.alphabeta(bb, pp, plies, width, nodes)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return round(1000.0 * ev[0].elapsed_time(ev[1]) / n, 2)
+
+    st, _, val, nd = E.alphabeta(b, p, plies, width, nodes)
+    out["us_per_launch"] = timed(b, p, reps)
+    worst = int(nd.argmax())
+    out["us_slowest_board_alone"] = timed(b[worst:worst + 1], p[worst:worst + 1], reps)
+    nd, val = nd.cpu().numpy(), val.cpu().numpy()
+    out.update(searched=int((st == 0).sum()), at_budget=int((st == 2).sum()), wins=int((val >= (1 << 39)).sum()),
+               losses=int((val <= -(1 << 39)).sum()), nodes_mean=round(float(nd.mean()), 2),
+               nodes_p99=int(np.percentile(nd, 99)), nodes_max=int(nd.max()))
+    out["us_per_node_slowest_board"] = round(out["us_slowest_board_alone"] / max(int(nd.max()), 1), 3)
+    return out
+
+
+def vcf_launch(size, boards, reps, seed, depth, nodes, scale=3e3):
+    """Microseconds per gmz_game_vcf launch on ``boards`` positions taken from games between two threat anchors
+    (noise scale 3e3, from the empty board, played by the numpy model tests/vcf_ref.py), by HIP events over ``reps``
+    launches; and the same launch on the slowest board alone, which bounds what one wave holds."""
+    import numpy as np
+    b, p = threat_positions(size, boards, seed, scale)
     out = dict(size=size, boards=boards, reps=reps, depth=depth, nodes=nodes)
 
     def timed(bb, pp, n):
@@ -122,11 +163,16 @@ def main():
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--b", default="self", help="side B: 'self' (the network against itself), anchor:threat, "
-                                                "anchor:uniform or anchor:vcf")
+                                                "anchor:uniform, anchor:vcf or anchor:ab; a comma-separated list "
+                                                "runs its sides in turn in every round (alternated runs)")
     ap.add_argument("--anchor-launch", type=int, default=0, metavar="REPS",
                     help="time the anchor launch alone on --slots boards over REPS launches, and stop")
-    ap.add_argument("--anchor-depth", type=int, default=None, help="anchor:vcf: attacker moves looked ahead (10)")
-    ap.add_argument("--anchor-nodes", type=int, default=None, help="anchor:vcf: node budget per board (2048)")
+    ap.add_argument("--anchor-depth", type=int, default=None, help="anchor:vcf / anchor:ab: attacker moves looked ahead (10)")
+    ap.add_argument("--anchor-nodes", type=int, default=None, help="anchor:vcf / anchor:ab: node budget per board (2048)")
+    ap.add_argument("--anchor-plies", type=int, default=None, help="anchor:ab: plies looked ahead (4)")
+    ap.add_argument("--anchor-width", type=int, default=None, help="anchor:ab: candidates per node (8)")
+    ap.add_argument("--ab-launch", type=int, default=0, metavar="REPS",
+                    help="time the alpha-beta launch alone on --slots positions over REPS launches, and stop")
     ap.add_argument("--vcf-launch", type=int, default=0, metavar="REPS",
                     help="time the solver launch alone on --slots positions over REPS launches, and stop")
     a = ap.parse_args()
@@ -134,17 +180,22 @@ def main():
         print(json.dumps(vcf_launch(a.size, a.slots, a.vcf_launch, a.seed, a.anchor_depth or E.VCF_DEPTH,
                                     a.anchor_nodes or E.VCF_NODES)), flush=True)
         return
+    if a.ab_launch:
+        print(json.dumps(ab_launch(a.size, a.slots, a.ab_launch, a.seed, a.anchor_plies or E.AB_PLIES,
+                                   a.anchor_width or E.AB_WIDTH, a.anchor_nodes or E.AB_NODES)), flush=True)
+        return
     if a.anchor_launch:
         print(json.dumps(anchor_launch(a.size, a.slots, a.anchor_launch, a.seed)), flush=True)
         return
     cfg = GmzConfig(BOARD_SIZE=a.size, NUM_SIMULATIONS=a.sims, NUM_RES_BLOCKS=a.blocks)
     sd = W.synthetic_state_dict(cfg, seed=a.seed, with_projection=False)
     for r in range(a.rounds):
-        for s in [int(x) for x in a.streams.split(",")]:
-            out = measure(cfg, sd, a.slots, s, a.steps, a.warmup, a.precision, a.seed, a.b, a.anchor_depth,
-                          a.anchor_nodes)
-            out["round"] = r
-            print(json.dumps(out), flush=True)
+        for side_b in a.b.split(","):
+            for s in [int(x) for x in a.streams.split(",")]:
+                out = measure(cfg, sd, a.slots, s, a.steps, a.warmup, a.precision, a.seed, side_b, a.anchor_depth,
+                              a.anchor_nodes, a.anchor_plies, a.anchor_width)
+                out["round"] = r
+                print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
