@@ -390,6 +390,29 @@ int gmz_net_workspace_bytes(const gmz_net_weights *w, int rows, size_t *out);
  * partials at a size its arguments imply, takes that buffer's size in bytes (workspace_bytes, ws_bytes, stats_bytes)
  * or slots (stats_slots) and fails with gmz_last_error() — before any launch — when the buffer is short (slots: when
  * they differ from what the launch writes, since the slot count is the partials' row stride). */
+/* Arithmetic of the inference network (tests/net_ref.py restates it in float64; tests/test_net_kernels_gpu.py holds the
+ * kernels to it bit for bit on data where it determines every bit).  W', b': the BatchNorm-folded weights and biases of
+ * gmz_net_pack below; e16: the 16-bit type `dtype`; an activation "as stored" is its e16 value.
+ *   stem, 3x3 convs   pre[p][o] = b'[o] + sum_t sum_c x[p + d(t)][c] * W16[o][c][t],  W16 = e16(W') (f16: clamped to
+ *                     +-65504 first), x the layer's input as stored (the stem: the 0/1 observation planes), tap
+ *                     t = 3 ky + kx reads the cell at offset d(t) = (ky - 1, kx - 1), cells off the board are zero;
+ *                     products of two e16 values are exact in f32 and are summed in f32, in no promised order
+ *     dynamics conv   + T[tap][o] (dyn_action, f32) on the cells q of the action's 3x3 window that are on the board,
+ *                     tap = (a - q) + (1, 1) as 3 dy + dx, T[tap][o] = sum_c W'[o][128 + c][tap] * embed[c]
+ *     conv2 of a block  + the block's input as stored
+ *   store             e16(pre), ONE rounding to nearest even of the f32 sum of all the terms above, then max(., +0) and,
+ *                     in f16, min(., 65504): never inf, never -0; f16 subnormals are kept, not flushed
+ *   head planes       relu(head_conv_b[o] + sum_c head_conv_w[o][c] * h[p][c]) in f32 over the hidden state as stored
+ *   logits            policy_fc_b[n] + sum_k policy_fc_w[n][k] * plane[k],  k = o * A + p over the two policy planes
+ *   value             v1 = relu(value_fc1_b + value_fc1_w . value plane), l = value_fc2_b + value_fc2_w . v1 (3 logits)
+ *   reward            r1 = relu(reward_fc1_b + e16(reward_fc.0) . h), k = c * A + p in the reference's order,
+ *                     l = reward_fc2_b + reward_fc2_w . r1
+ *   support_to_scalar softmax(l) . (-1, 0, 1) in f32: expf(l - max l), two additions, three divisions; the only step
+ *                     that is not exact on exact data: within 16 * 2^-24 of the float64 value
+ * Where every term of a sum is a multiple of a quantum q and the sum of the terms' absolute values stays below 2^24 q,
+ * every partial sum is exact in f32 in any order, fused or not, so `store` rounds the exact sum and the f32 results are
+ * the exact values.  Rows are independent: a row's outputs do not depend on the other rows, on rows skipped, on the grid
+ * or on max_grid.  A skipped row's logits, value, reward and every pool slot that no live row names are not written. */
 /* network.py:137-143 initial_inference: obs_dev f32[rows][3][A] -> logits f32[rows][A],
  * value f32[rows] (support_to_scalar), hidden state -> hid_pool_dev[out_slot[r]] (dtype [A][C]).
  * Rows with out_slot[r] < 0 are skipped. */

@@ -197,6 +197,28 @@ def test_skipped_rows_untouched(mods):
     lg, v, _ = net.initial_inference(obs, slots=[0, -1])
     torch.cuda.synchronize()
     assert torch.isfinite(lg[0]).all()
+    # the same through the backend interface, on buffers whose contents are known: slot 1 live, slots 0, 2, 3 not
+    # named; logits, value and reward start as NaN.  The live row ends finite; the skipped row's outputs and every
+    # slot not named are untouched, in the initial and in the recurrent pass.
+    from datou_gomoku_muzero_amd import _lib
+    dev = net.device
+    i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    net.pool.fill_(-91)  # 0xFFA5: a NaN in f16
+    lg, v = nan(2, 81), nan(2)
+    net.initial(torch.from_numpy(obs).to(dev), i32([1, -1]), lg, v, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    pool = net.pool.view(4, -1).cpu().numpy()
+    assert (pool[[0, 2, 3]] == -91).all() and np.isfinite(net.hidden([1]).cpu().numpy()).all()
+    assert torch.isfinite(lg[0]).all() and torch.isfinite(v[0]) and torch.isnan(lg[1]).all() and torch.isnan(v[1])
+    lg, v, r = nan(2, 81), nan(2), nan(2)
+    net.recurrent(i32([1, 1]), i32([40, 7]), i32([-1, 3]), lg, v, r, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    after = net.pool.view(4, -1).cpu().numpy()
+    assert (after[[0, 2]] == -91).all() and np.array_equal(after[1], pool[1])
+    assert np.isfinite(net.hidden([3]).cpu().numpy()).all()
+    assert torch.isfinite(lg[1]).all() and torch.isfinite(v[1]) and torch.isfinite(r[1])
+    assert torch.isnan(lg[0]).all() and torch.isnan(v[0]) and torch.isnan(r[0])
 
 
 @pytest.mark.parametrize("size,sims,mode,blocks,G", [(15, 400, "MuZero", 2, 6), (9, 50, "AlphaZero", 1, 6),
