@@ -178,6 +178,14 @@ def nbytes(t):
     return 0 if t is None else t.numel() * t.element_size()
 
 
+def bufs(*tensors):
+    """(pointer, bytes held) of each tensor in turn, (NULL, 0) for None: the checked buffers of an entry point."""
+    out = []  # spelled out: a launch of a few microseconds is bound by the host
+    for t in tensors:
+        out += (None, 0) if t is None else (ctypes.c_void_p(t.data_ptr()), t.numel() * t.element_size())
+    return out
+
+
 def stream_ptr(stream=None):
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)

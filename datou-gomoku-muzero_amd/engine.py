@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .config import from_any
-from ._lib import GmzError, check, ptr
+from ._lib import GmzError, bufs, check, ptr
 from .openings import _has_five, _place_stones, random_openings, seeded_openings  # noqa: F401  (re-exported)
 
 
@@ -574,14 +574,8 @@ class BatchedSelfPlayEngine:
         engine's own device boards, in one launch on ``stream`` with no host wait: into ``self.action``, which is
         returned and which play_refill(action=...) takes.  ``noise``: f64[G,A] on the device (keyed_gumbel's) or
         None.  On an engine that play_refill drives, an idle slot gets -1."""
-        if noise is not None and (not torch.is_tensor(noise) or noise.dtype != torch.float64
-                                  or noise.device.type != self.device.type or not noise.is_contiguous()):
-            raise ValueError("anchor_move: noise must be a contiguous float64 tensor on %s" % self.device)
-        boards, players, game = self._game_ptrs()
-        check(self.lib.gmz_game_anchor_move(
-            boards, players, game, ptr(noise), _lib.nbytes(noise), self.G, self.size,
-            self.cfg.N_IN_ROW, anchor_kind(kind), float(scale), ptr(self.action), _lib.nbytes(self.action), None, 0,
-            self._stream(stream)))
+        _call_anchor_move(self.lib, self._game_ptrs(), self.G, self.size, self.cfg.N_IN_ROW,
+                          _noise_arg("anchor_move", noise, self.device), kind, scale, self.action, None, stream)
         return self.action
 
     def vcf_move(self, depth=None, nodes=None, stream=None):
@@ -590,14 +584,10 @@ class BatchedSelfPlayEngine:
         ``self.action`` (after anchor_move: the threat rule's move), every other entry stays.  Returns
         ``self.action``; the statuses and moves of the launch stay in ``self.vcf_status`` / ``self.vcf_moves``."""
         if self.vcf_status is None:
-            self.vcf_status = torch.zeros(self.G, dtype=torch.int8, device=self.device)
-            self.vcf_moves = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
-        boards, players, game = self._game_ptrs()
-        check(self.lib.gmz_game_vcf(
-            boards, players, game, self.G, self.size, self.cfg.N_IN_ROW,
-            VCF_DEPTH if depth is None else int(depth), VCF_NODES if nodes is None else int(nodes),
-            ptr(self.vcf_status), _lib.nbytes(self.vcf_status), ptr(self.vcf_moves), _lib.nbytes(self.vcf_moves),
-            None, 0, None, 0, ptr(self.action), _lib.nbytes(self.action), self._stream(stream)))
+            self.vcf_status, self.vcf_moves = _status_pair(self.G, self.device)
+        outs = self.vcf_status, self.vcf_moves, None, None, self.action
+        _call_vcf(self.lib, self._game_ptrs(), self.G, self.size, self.cfg.N_IN_ROW,
+                  VCF_DEPTH if depth is None else depth, VCF_NODES if nodes is None else nodes, outs, stream)
         return self.action
 
     def ab_move(self, noise=None, scale=0.0, plies=None, width=None, nodes=None, stream=None):
@@ -606,19 +596,12 @@ class BatchedSelfPlayEngine:
         entry of ``self.action`` (after anchor_move: the threat rule's move), every other entry stays.  ``noise``:
         f64[G,A] on the device (keyed_gumbel's) or None.  Returns ``self.action``; the statuses and moves of the
         launch stay in ``self.ab_status`` / ``self.ab_moves``."""
-        if noise is not None and (not torch.is_tensor(noise) or noise.dtype != torch.float64
-                                  or noise.device.type != self.device.type or not noise.is_contiguous()):
-            raise ValueError("ab_move: noise must be a contiguous float64 tensor on %s" % self.device)
         if self.ab_status is None:
-            self.ab_status = torch.zeros(self.G, dtype=torch.int8, device=self.device)
-            self.ab_moves = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
-        boards, players, game = self._game_ptrs()
-        check(self.lib.gmz_game_alphabeta(
-            boards, players, game, ptr(noise), _lib.nbytes(noise), float(scale), self.G, self.size, self.cfg.N_IN_ROW,
-            AB_PLIES if plies is None else int(plies), AB_WIDTH if width is None else int(width),
-            AB_NODES if nodes is None else int(nodes), ptr(self.ab_status), _lib.nbytes(self.ab_status),
-            ptr(self.ab_moves), _lib.nbytes(self.ab_moves), None, 0, None, 0, ptr(self.action),
-            _lib.nbytes(self.action), self._stream(stream)))
+            self.ab_status, self.ab_moves = _status_pair(self.G, self.device)
+        outs = self.ab_status, self.ab_moves, None, None, self.action
+        _call_alphabeta(self.lib, self._game_ptrs(), self.G, self.size, self.cfg.N_IN_ROW,
+                        _noise_arg("ab_move", noise, self.device), scale, AB_PLIES if plies is None else plies,
+                        AB_WIDTH if width is None else width, AB_NODES if nodes is None else nodes, outs, stream)
         return self.action
 
     def winning_scan(self, boards, players, action=None, counters=None, stream=None):
@@ -979,7 +962,45 @@ def winning_scan(boards, players, actions=None, n_in_row=5, counters=None, strea
     return cls
 
 
+def _noise_arg(who, noise, device):
+    """An engine method's ``noise`` as it is, once checked: None, or a contiguous float64 tensor on ``device``."""
+    if noise is not None and (not torch.is_tensor(noise) or noise.dtype != torch.float64
+                              or noise.device.type != device.type or not noise.is_contiguous()):
+        raise ValueError("%s: noise must be a contiguous float64 tensor on %s" % (who, device))
+    return noise
+
+
+def _actions_arg(who, actions, device):
+    """A search's ``actions`` as it is, once checked: None, or a contiguous int32 tensor on ``device``."""
+    if actions is not None and (not torch.is_tensor(actions) or actions.dtype != torch.int32
+                                or actions.device != device or not actions.is_contiguous()):
+        raise ValueError("%s: actions must be a contiguous int32 tensor on the boards' device (updated in place)" % who)
+    return actions
+
+
+def _status_pair(G, device):
+    """The (status int8[G], moves int32[G]) that a search launch on an engine's own boards leaves behind."""
+    return torch.zeros(G, dtype=torch.int8, device=device), torch.full((G,), -1, dtype=torch.int32, device=device)
+
+
+# One caller per anchor entry point spells its argument list (include/gmz.h).  state: (boards, players, game) pointers
+def _call_anchor_move(L, state, G, S, n, noise, kind, scale, actions, scores, stream):
+    check(L.gmz_game_anchor_move(*state, *bufs(noise), G, S, int(n), anchor_kind(kind), float(scale),
+                                 *bufs(actions, scores), _lib.stream_ptr(stream)))
+
+
+def _call_vcf(L, state, G, S, n, depth, nodes, outs, stream):
+    check(L.gmz_game_vcf(*state, G, S, int(n), int(depth), int(nodes), *bufs(*outs), _lib.stream_ptr(stream)))
+
+
+def _call_alphabeta(L, state, G, S, n, noise, scale, plies, width, nodes, outs, stream):
+    check(L.gmz_game_alphabeta(*state, *bufs(noise), float(scale), G, S, int(n), int(plies), int(width), int(nodes),
+                               *bufs(*outs), _lib.stream_ptr(stream)))
+
+
 ANCHOR_KINDS = {"threat": 0, "uniform": 1}
+VCF_DEPTH, VCF_NODES = 10, 2048  # the solver's defaults (DESIGN.md §8b)
+AB_PLIES, AB_WIDTH, AB_NODES = 4, 8, 2048  # the alpha-beta anchor's defaults (DESIGN.md §8b)
 
 
 def anchor_kind(kind):
@@ -1000,18 +1021,12 @@ def anchor_move(boards, players, noise=None, kind="threat", scale=0.0, n_in_row=
     player whose ties the noise breaks.  ``game`` int32[G]: a negative entry leaves that board out.  Returns
     actions int32[G] (-1: full board or left out), or (actions, scores int64[G,S*S]) with ``scores`` (-1 for an
     occupied cell)."""
-    L = _lib.load()
     b, p, gm, G, S = _board_args("anchor_move", boards, players, game)
     nz = None if noise is None else torch.as_tensor(noise, dtype=torch.float64).to(b.device).contiguous()
     act = torch.empty(G, dtype=torch.int32, device=b.device)
     sc = torch.empty(G, S * S, dtype=torch.int64, device=b.device) if scores else None
-    check(L.gmz_game_anchor_move(ptr(b), ptr(p), ptr(gm), ptr(nz), _lib.nbytes(nz), G, S, int(n_in_row),
-                                 anchor_kind(kind), float(scale), ptr(act), _lib.nbytes(act), ptr(sc), _lib.nbytes(sc),
-                                 _lib.stream_ptr(stream)))
+    _call_anchor_move(_lib.load(), (ptr(b), ptr(p), ptr(gm)), G, S, n_in_row, nz, kind, scale, act, sc, stream)
     return (act, sc) if scores else act
-
-
-VCF_DEPTH, VCF_NODES = 10, 2048  # the solver's defaults (DESIGN.md §8b)
 
 
 def vcf(boards, players, depth=VCF_DEPTH, nodes=VCF_NODES, game=None, actions=None, stream=None, n_in_row=5):
@@ -1023,20 +1038,11 @@ def vcf(boards, players, depth=VCF_DEPTH, nodes=VCF_NODES, game=None, actions=No
     ``actions`` int32[G] on the device is updated in place: entry g becomes the solver's move where it found a win
     and stays as it is everywhere else.  Returns (status int8[G]: 0 none, 1 found, 2 node budget used up, 3 skipped;
     move int32[G], -1 unless status is 1; length int32[G], the attacker moves of the line; nodes int32[G])."""
-    L = _lib.load()
     b, p, gm, G, S = _board_args("vcf", boards, players, game)
-    if actions is not None and (not torch.is_tensor(actions) or actions.dtype != torch.int32
-                                or actions.device != b.device or not actions.is_contiguous()):
-        raise ValueError("vcf: actions must be a contiguous int32 tensor on the boards' device (updated in place)")
-    st = torch.empty(G, dtype=torch.int8, device=b.device)
-    mv, ln, nd = (torch.empty(G, dtype=torch.int32, device=b.device) for _ in range(3))
-    check(L.gmz_game_vcf(ptr(b), ptr(p), ptr(gm), G, S, int(n_in_row), int(depth), int(nodes), ptr(st), _lib.nbytes(st),
-                         ptr(mv), _lib.nbytes(mv), ptr(ln), _lib.nbytes(ln), ptr(nd), _lib.nbytes(nd), ptr(actions),
-                         _lib.nbytes(actions), _lib.stream_ptr(stream)))
+    actions = _actions_arg("vcf", actions, b.device)
+    st, mv, ln, nd = (torch.empty(G, dtype=d, device=b.device) for d in (torch.int8,) + 3 * (torch.int32,))
+    _call_vcf(_lib.load(), (ptr(b), ptr(p), ptr(gm)), G, S, n_in_row, depth, nodes, (st, mv, ln, nd, actions), stream)
     return st, mv, ln, nd
-
-
-AB_PLIES, AB_WIDTH, AB_NODES = 4, 8, 2048  # the alpha-beta anchor's defaults (DESIGN.md §8b)
 
 
 def alphabeta(boards, players, plies=AB_PLIES, width=AB_WIDTH, nodes=AB_NODES, noise=None, scale=0.0, game=None,
@@ -1051,18 +1057,11 @@ def alphabeta(boards, players, plies=AB_PLIES, width=AB_WIDTH, nodes=AB_NODES, n
     stays as it is everywhere else.  Returns (status int8[G]: 0 searched, 2 node budget used up, 3 skipped or a full
     board; move int32[G], -1 unless status is 0; value int64[G], the root's value from the mover's side; nodes
     int32[G])."""
-    L = _lib.load()
     b, p, gm, G, S = _board_args("alphabeta", boards, players, game)
-    if actions is not None and (not torch.is_tensor(actions) or actions.dtype != torch.int32
-                                or actions.device != b.device or not actions.is_contiguous()):
-        raise ValueError("alphabeta: actions must be a contiguous int32 tensor on the boards' device (updated in "
-                         "place)")
+    actions = _actions_arg("alphabeta", actions, b.device)
     nz = None if noise is None else torch.as_tensor(noise, dtype=torch.float64).to(b.device).contiguous()
-    st = torch.empty(G, dtype=torch.int8, device=b.device)
-    mv, nd = (torch.empty(G, dtype=torch.int32, device=b.device) for _ in range(2))
-    val = torch.empty(G, dtype=torch.int64, device=b.device)
-    check(L.gmz_game_alphabeta(ptr(b), ptr(p), ptr(gm), ptr(nz), _lib.nbytes(nz), float(scale), G, S, int(n_in_row),
-                               int(plies), int(width), int(nodes), ptr(st), _lib.nbytes(st), ptr(mv), _lib.nbytes(mv),
-                               ptr(val), _lib.nbytes(val), ptr(nd), _lib.nbytes(nd), ptr(actions),
-                               _lib.nbytes(actions), _lib.stream_ptr(stream)))
+    st, mv, val, nd = (torch.empty(G, dtype=d, device=b.device)
+                       for d in (torch.int8, torch.int32, torch.int64, torch.int32))
+    _call_alphabeta(_lib.load(), (ptr(b), ptr(p), ptr(gm)), G, S, n_in_row, nz, scale, plies, width, nodes,
+                    (st, mv, val, nd, actions), stream)
     return st, mv, val, nd

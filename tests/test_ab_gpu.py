@@ -3,7 +3,8 @@ arena.AnchorPlayer("ab")).  Every comparison is exact: status, move, value and n
 and the numpy model (tests/ab_ref.py) must give alike, since both walk the same tree in the same order.
 
   1. kernel against model on positions of model games between two threat anchors (noise scale 3e3, from the empty
-     board: vcf_ref.threat_game_positions), 6x6 to 22x22, n = 4 and 5, in guarded buffers, budget 2,048;
+     board: vcf_ref.threat_game_positions), 6x6 to 22x22, n = 4 and 5, in guarded buffers, budget 2,048; and at the
+     edge shapes 5x5 with n = 5, 8x8 with n = 8 and 7x7 with n = 3;
   2. the limits: plies 1 and 8, width 1 and 16, max_nodes 1, 8 and 64 on the 9x9 batch of 65;
   3. the root's order under a noise row at scale 0 and 3e3, and ties without noise;
   4. game_dev with negative entries, actions_dev in/out, the nullable outputs, the hand-built positions;
@@ -30,7 +31,8 @@ pytestmark = pytest.mark.gpu
 NODES = 2048
 # (size, n): (model games, seed) of the position pool.  The seeds are chosen so that the model's own results meet the
 # conditions asserted in test 1 (seed 1 does everywhere).
-POOLS = {(6, 4): (19, 1), (9, 5): (8, 1), (15, 5): (3, 1), (19, 5): (1, 1), (22, 5): (1, 1), (6, 5): (7, 1)}
+POOLS = {(6, 4): (19, 1), (9, 5): (8, 1), (15, 5): (3, 1), (19, 5): (1, 1), (22, 5): (1, 1), (6, 5): (7, 1),
+         (5, 5): (40, 1), (8, 8): (12, 1), (7, 3): (200, 1)}
 ALL = 0  # a batch of the whole pool
 
 
@@ -178,6 +180,28 @@ def test_kernel_equals_the_model(mods, S, n, G, plies, width):
         assert st.size == 1 and wins == 1
     got = run_kernel(mods, b, p, n, plies, width, NODES)
     assert_equal(got, want, (S, n, G, plies, width))
+
+
+@pytest.mark.parametrize("S,n", [(5, 5), (8, 8), (7, 3)], ids=["5x5-n5", "8x8-n8", "7x7-n3"])
+def test_kernel_equals_the_model_at_the_edge_shapes(mods, S, n):
+    """n equal to the board size (a line is its own single window; 8 is the search's largest n) and n = 3, the
+    smallest: 65 evenly spaced positions each, plies 3, width 6.  Conditions on the model's own results.  With n = S
+    wins hardly exist, so there: every board searched, none at the node budget, at least 10 moves differ from the
+    threat rule's.  With n = 3 on 7x7: at least 3 wins seen below the root and at least 5 losses."""
+    plies, width = 3, 6
+    b, p = pool(S, n, 65)
+    want = reference(S, n, 65, plies, width)
+    st, mv, val, nd = want
+    differ, wins = int(((mv != threat_moves(S, n, 65)) & (st == AB.SEARCHED)).sum()), int(deep_wins(val, plies).sum())
+    losses, spent = int((val <= -(AB.WIN - plies)).sum()), int((st == AB.BUDGET).sum())
+    print("%dx%d n %d: %d positions, %d searched, %d moves differ, %d wins below the root, %d losses, %d at the budget, "
+          "nodes max %d" % (S, S, n, st.size, (st == AB.SEARCHED).sum(), differ, wins, losses, spent, nd.max()))
+    assert st.size == 65
+    if n == S:
+        assert (st == AB.SEARCHED).all() and spent == 0 and differ >= 10
+    else:
+        assert wins >= 3 and losses >= 5
+    assert_equal(run_kernel(mods, b, p, n, plies, width, NODES), want, (S, n, plies, width))
 
 
 # ---------------------------------------------------------------------------------------------- 2. limits

@@ -51,6 +51,17 @@ def hand_built():
     edge = _board(S, [(0, 6), (0, 7), (0, 8), (1, 5), (2, 5), (3, 5)], [(0, 3)] + _SPREAD[:5])
     cases.append(("four against the edge", edge, 1, 5, 10, 2048, (V.FOUND, 5, 2), None))
     cases.append(("four against the edge, depth 1", edge, 1, 5, 1, 2048, (V.NONE, -1, 0), 1))
+    # 5x5 with n = 5: a line of five cells is its own single window (n equal to the board size).  Four stones of the
+    # attacker and one empty cell in it: a five on that cell, in a row, a column and on either diagonal
+    for what, cells, hole in (("row", [(2, c) for c in range(5)], 3), ("column", [(r, 1) for r in range(5)], 0),
+                              ("diagonal", [(i, i) for i in range(5)], 2),
+                              ("anti-diagonal", [(i, 4 - i) for i in range(5)], 4)):
+        r, c = cells[hole]
+        one = _board(5, [x for x in cells if x != (r, c)])
+        cases.append(("5x5 single window, " + what, one, 1, 5, 10, 2048, (V.FOUND, r * 5 + c, 1), 1))
+    # the same window held by the defender and nothing else on the board: the one block is no four, so no win
+    theirs = _board(5, [], [(2, c) for c in range(5) if c != 3])
+    cases.append(("5x5 single window, the defender's", theirs, 1, 5, 10, 2048, (V.NONE, -1, 0), 1))
     # 6x6, four in a row: (0,0) makes a four along row 0 (reply (0,3)) and down column 0 (reply (3,0))
     small = _board(6, [(0, 1), (0, 2), (1, 0), (2, 0)], [(5, 5), (3, 5), (5, 3), (4, 1)])
     cases.append(("n_in_row 4 on 6x6", small, 1, 4, 10, 2048, (V.FOUND, 0, 2), 1))

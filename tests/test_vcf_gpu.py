@@ -3,7 +3,7 @@ exact: status, move, length and node count are integers that the kernel and the 
 give alike, since both walk the same tree in the same order.
 
   1. kernel against model on every position of model games between two threat anchors (noise scale 3e3, from the
-     empty board), 6x6 to 22x22, n = 4 and 5, 1 / 65 / about 1,000 boards, in guarded buffers;
+     empty board), 5x5 to 22x22, n = 3, 4 and 5, 1 / 65 / about 1,000 boards, in guarded buffers;
   2. the limits: max_depth 1, 2, 16 and max_nodes 1, 8, 64 on the 9x9 set;
   3. the hand-built positions of tests/test_vcf.py;
   4. game_dev with negative entries, actions_dev in/out, the nullable outputs;
@@ -26,7 +26,8 @@ pytestmark = pytest.mark.gpu
 DEPTH, NODES = 10, 4096  # the default case's limits (the entry point's own default budget is 2,048 nodes)
 # (size, n): (model games, seed) of the position pool.  The seeds are chosen so that the model's own results meet the
 # conditions asserted in test 1 (seed 1 does everywhere).
-POOLS = {(6, 4): (75, 1), (6, 5): (34, 1), (9, 5): (32, 1), (15, 5): (26, 1), (19, 5): (8, 1), (22, 5): (8, 1)}
+POOLS = {(6, 4): (75, 1), (6, 5): (34, 1), (9, 5): (32, 1), (15, 5): (26, 1), (19, 5): (8, 1), (22, 5): (8, 1),
+         (7, 3): (200, 1), (5, 4): (60, 1)}
 ALL = 0  # a batch of the whole pool
 
 
@@ -110,7 +111,8 @@ def assert_equal(got, want, what):
 
 # ---------------------------------------------------------------------------------------------- 1. kernel against model
 CASES = [(6, 4, 1), (6, 4, 65), (6, 4, ALL), (6, 5, 1), (6, 5, 65), (6, 5, ALL), (9, 5, 1), (9, 5, 65), (9, 5, ALL),
-         (15, 5, ALL), (19, 5, 65), (22, 5, 65)]
+         (15, 5, ALL), (19, 5, 65), (22, 5, 65),
+         (7, 3, 65), (5, 4, 65)]  # n = 3, the solver's lower limit, and the smallest board: windows clipped on every side
 
 
 @pytest.mark.parametrize("S,n,G", CASES, ids=["%dx%d-n%d-G%s" % (c[0], c[0], c[1], c[2] or "all") for c in CASES])

@@ -52,6 +52,31 @@ def measure(cfg, sd, slots, streams, steps, warmup, precision, seed, side_b="sel
     return out
 
 
+def timed_launches(fn, warmup, reps):
+    """Microseconds per call of ``fn``, by two HIP events around ``reps`` calls after ``warmup`` calls."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(reps):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return round(1000.0 * ev[0].elapsed_time(ev[1]) / reps, 2)
+
+
+def launch_then_slowest(search, b, p, warmup, reps, out):
+    """One ``search(boards, players)`` launch for its results (the fourth: nodes per board), then into ``out`` its time
+    on all boards and on the board of the most nodes alone, which bounds what one wave holds.  Returns the results."""
+    res = search(b, p)
+    out["us_per_launch"] = timed_launches(lambda: search(b, p), warmup, reps)
+    worst = int(res[3].argmax())
+    bw, pw = b[worst:worst + 1], p[worst:worst + 1]
+    out["us_slowest_board_alone"] = timed_launches(lambda: search(bw, pw), warmup, reps)
+    return res
+
+
 def anchor_launch(size, boards, reps, seed):
     """Microseconds per gmz_game_anchor_move launch on ``boards`` mid-game boards, by HIP events over ``reps``
     launches (threat rule with Gumbel noise, and the uniform rule)."""
@@ -62,16 +87,7 @@ def anchor_launch(size, boards, reps, seed):
     noise = torch.from_numpy(rs.gumbel(0, 1, (boards, size * size))).cuda()
     out = dict(size=size, boards=boards, reps=reps)
     for kind, scale in (("threat", 0.0), ("uniform", 1.0)):
-        for _ in range(10):
-            E.anchor_move(b, p, noise, kind, scale)
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(reps):
-            E.anchor_move(b, p, noise, kind, scale)
-        ev[1].record()
-        torch.cuda.synchronize()
-        out["us_per_launch_" + kind] = round(1000.0 * ev[0].elapsed_time(ev[1]) / reps, 2)
+        out["us_per_launch_" + kind] = timed_launches(lambda: E.anchor_move(b, p, noise, kind, scale), 10, reps)
     return out
 
 
@@ -95,23 +111,7 @@ def ab_launch(size, boards, reps, seed, plies, width, nodes):
     import numpy as np
     b, p = threat_positions(size, boards, seed)
     out = dict(size=size, boards=boards, reps=reps, plies=plies, width=width, nodes=nodes)
-
-    def timed(bb, pp, n):
-        for _ in range(2):
-            E.alphabeta(bb, pp, plies, width, nodes)
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(n):
-            E.alphabeta(bb, pp, plies, width, nodes)
-        ev[1].record()
-        torch.cuda.synchronize()
-        return round(1000.0 * ev[0].elapsed_time(ev[1]) / n, 2)
-
-    st, _, val, nd = E.alphabeta(b, p, plies, width, nodes)
-    out["us_per_launch"] = timed(b, p, reps)
-    worst = int(nd.argmax())
-    out["us_slowest_board_alone"] = timed(b[worst:worst + 1], p[worst:worst + 1], reps)
+    st, _, val, nd = launch_then_slowest(lambda bb, pp: E.alphabeta(bb, pp, plies, width, nodes), b, p, 2, reps, out)
     nd, val = nd.cpu().numpy(), val.cpu().numpy()
     out.update(searched=int((st == 0).sum()), at_budget=int((st == 2).sum()), wins=int((val >= (1 << 39)).sum()),
                losses=int((val <= -(1 << 39)).sum()), nodes_mean=round(float(nd.mean()), 2),
@@ -123,27 +123,11 @@ def ab_launch(size, boards, reps, seed, plies, width, nodes):
 def vcf_launch(size, boards, reps, seed, depth, nodes, scale=3e3):
     """Microseconds per gmz_game_vcf launch on ``boards`` positions taken from games between two threat anchors
     (noise scale 3e3, from the empty board, played by the numpy model tests/vcf_ref.py), by HIP events over ``reps``
-    launches; and the same launch on the slowest board alone, which bounds what one wave holds."""
+    launches; and the same launch on the slowest board alone."""
     import numpy as np
     b, p = threat_positions(size, boards, seed, scale)
     out = dict(size=size, boards=boards, reps=reps, depth=depth, nodes=nodes)
-
-    def timed(bb, pp, n):
-        for _ in range(3):
-            E.vcf(bb, pp, depth, nodes)
-        torch.cuda.synchronize()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(n):
-            E.vcf(bb, pp, depth, nodes)
-        ev[1].record()
-        torch.cuda.synchronize()
-        return round(1000.0 * ev[0].elapsed_time(ev[1]) / n, 2)
-
-    st, _, ln, nd = E.vcf(b, p, depth, nodes)
-    out["us_per_launch"] = timed(b, p, reps)
-    worst = int(nd.argmax())
-    out["us_slowest_board_alone"] = timed(b[worst:worst + 1], p[worst:worst + 1], reps)
+    st, _, ln, nd = launch_then_slowest(lambda bb, pp: E.vcf(bb, pp, depth, nodes), b, p, 3, reps, out)
     nd = nd.cpu().numpy()
     out.update(wins=int((st == 1).sum()), wins_len3=int(((st == 1) & (ln >= 3)).sum()), at_budget=int((st == 2).sum()),
                nodes_mean=round(float(nd.mean()), 2), nodes_p99=int(np.percentile(nd, 99)), nodes_max=int(nd.max()))
