@@ -909,12 +909,16 @@ __device__ int select_nonroot_cl(const Dev &D, const uint64_t (&lg)[NJ], int lm,
 }
 
 // Gumbel(0, 1) sample of (seed, move counter, game key, action): the device noise of k_begin_move and
-// k_gumbel_keyed (mcts.py:312, np.random.gumbel)
+// k_gumbel_keyed (mcts.py:312, np.random.gumbel).  tests/noise_ref.py restates it, tests/test_noise.py states its
+// statistics.  A sample is a function of h2 alone: 32 bits of entropy spread over the 53-bit mantissa.  A row is
+// a function of h1 and the seed's high word: 2^32 distinct rows per high word.  (counter, key) enters through one
+// 32-bit sum, and two pairs with equal sums draw the same row: within 1,023 moves the nearest are 2,886,698 keys
+// apart.
 __device__ __forceinline__ double gumbel_noise(uint64_t seed, uint32_t counter, uint32_t key, int a) {
   const uint32_t h1 = mix32((uint32_t)seed ^ mix32(counter * 0x9E3779B1u + key * 0x85EBCA77u));
   const uint32_t h2 = mix32(h1 ^ mix32((uint32_t)a + 0x68E31DA4u) ^ (uint32_t)(seed >> 32));
   const uint32_t h3 = mix32(h2 + 0x1B873593u);
-  const uint64_t bits = ((uint64_t)h2 << 21) ^ (uint64_t)h3;  // 53 random bits
+  const uint64_t bits = ((uint64_t)h2 << 21) ^ (uint64_t)h3;  // 53 bits from the 32 of h2
   double u = (double)(bits & ((1ull << 53) - 1)) * 0x1.0p-53;
   if (u <= 0.0) u = 0x1.0p-53;
   return -log(-log(1.0 - u));
