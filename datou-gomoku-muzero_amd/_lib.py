@@ -66,6 +66,7 @@ _SIGS = {
     "gmz_engine_set_budgets": ([P, P, SZ, P], I),
     "gmz_engine_waves_for_budgets": ([ctypes.POINTER(EngineCfg), P, P, I, P, P], I),
     "gmz_engine_play_refill": ([P, P, P, P, P, P, P, I, P, I, P, P, P, P, I, P, P, P, I, I, P, P], I),
+    "gmz_engine_play_book": ([P, P, P, P, SZ, P, SZ, P, SZ, P, SZ, I, U64, I, P, P, I, P, SZ, P], I),
     "gmz_replay_ingest": ([I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, P, SZ, P, P, P], I),
     "gmz_replay_positions": ([I, I, I, P, SZ, P, I, P, SZ, I, P, SZ, P, SZ, P, SZ, P, SZ, P], I),
     "gmz_replay_rewrite": ([I, I, I, I, P, SZ, P, SZ, P, SZ, P, SZ, I, P, I, P, SZ, P, P], I),

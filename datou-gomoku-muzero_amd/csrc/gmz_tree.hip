@@ -1896,6 +1896,62 @@ __global__ void k_play_refill(Dev D, int n_in_row, RefillArgs R) {
   R.n_legal[g] = id >= 0 ? A - D.move_counts[g] : 0;
 }
 
+// One word of the opening-book draw (gmz_engine_play_book): a function of (seed, key, serial, salt), the row word
+// built as gumbel_noise's h1 is; the salts (gmz.h) keep it apart from every noise word.
+__host__ __device__ __forceinline__ uint32_t book_word(uint64_t seed, uint32_t serial, uint32_t key, uint32_t salt) {
+  const uint32_t h1 = mix32((uint32_t)seed ^ mix32(serial * 0x9E3779B1u + key * 0x85EBCA77u));
+  return mix32(h1 ^ (uint32_t)(seed >> 32) ^ salt);
+}
+
+// cell (r, c) of a size x size board under symmetry d: bit 0 transposes, then bit 1 flips r, then bit 2 flips c
+__host__ __device__ __forceinline__ int book_map(int cell, int size, int d) {
+  int r = cell / size, c = cell % size;
+  if (d & 1) { const int t = r; r = c; c = t; }
+  if (d & 2) r = size - 1 - r;
+  if (d & 4) c = size - 1 - c;
+  return r * size + c;
+}
+
+// k_play_engine (no reset) + self-play's restart from an opening book (gmz_engine_play_book): one thread per slot
+struct BookArgs {
+  const int32_t *actions;
+  int8_t *status;
+  const int8_t *book_boards, *book_players;
+  const int32_t *book_last, *book_counts;
+  int n_openings, symmetry;
+  uint64_t seed;
+  int32_t *slot_serial, *slot_draw, *tally;
+};
+
+__global__ void k_play_book(Dev D, int n_in_row, BookArgs B) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= D.G) return;
+  const int A = D.A;
+  int8_t *b = D.boards + (size_t)g * A;
+  int8_t st;
+  play_one(b, D.size, n_in_row, D.players + g, D.last_moves + g, D.move_counts + g, B.actions[g], &st, 0);
+  B.status[g] = st;
+  int serial = B.slot_serial[g];
+  const bool ended = st != 2 && st != 3;
+  if (!ended && serial != -1) return;
+  if (ended && serial >= 0 && B.tally) {  // the ended game's opening, before the draw is overwritten
+    const int t0 = B.slot_draw[g] >> 3;
+    if (t0 >= 0 && t0 < B.n_openings) atomicAdd(B.tally + 3 * (size_t)t0 + (st == 1 ? 0 : st == -1 ? 1 : 2), 1);
+  }
+  serial += 1;
+  const uint32_t key = (uint32_t)(g + D.game_offset);
+  const int t = (int)(((uint64_t)book_word(B.seed, (uint32_t)serial, key, GMZ_BOOK_SALT_OPEN) * (uint64_t)B.n_openings) >> 32);
+  const int d = B.symmetry ? (int)(book_word(B.seed, (uint32_t)serial, key, GMZ_BOOK_SALT_SYM) & 7u) : 0;
+  const int8_t *ob = B.book_boards + (size_t)t * A;
+  for (int i = 0; i < A; ++i) b[book_map(i, D.size, d)] = ob[i];
+  const int lm = B.book_last[t];
+  D.players[g] = B.book_players[t];
+  D.last_moves[g] = lm >= 0 && lm < A ? book_map(lm, D.size, d) : -1;
+  D.move_counts[g] = B.book_counts[t];
+  B.slot_serial[g] = serial;
+  B.slot_draw[g] = 8 * t + d;
+}
+
 __global__ void k_gumbel_keyed(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ plies, uint64_t seed,
                                int G, int A, double *__restrict__ out) {
   const int g = blockIdx.y;
@@ -2382,6 +2438,42 @@ GMZ_EXPORT int gmz_engine_play_refill(gmz_engine *e, const int32_t *action, int8
   hipLaunchKernelGGL(k_play_refill, dim3((e->D.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->D, e->n_in_row, R);
   GMZ_LAUNCH_CHECK();
   e->active = e->active_buf;  // every slot's byte was written by the launch
+  return 0;
+}
+
+GMZ_EXPORT int gmz_engine_play_book(gmz_engine *e, const int32_t *action, int8_t *status, const int8_t *book_boards,
+                                    size_t boards_bytes, const int8_t *book_players, size_t players_bytes,
+                                    const int32_t *book_last, size_t last_bytes, const int32_t *book_counts,
+                                    size_t counts_bytes, int n_openings, uint64_t seed, int symmetry,
+                                    int32_t *slot_serial, int32_t *slot_draw, int slot_capacity, int32_t *tally,
+                                    size_t tally_bytes, void *stream) {
+  // everything that does not need the engine first: a bad call is refused whatever the handle
+  if (!e || !action || !status) return fail("gmz_engine_play_book: null engine, action or status");
+  if (!book_boards || !book_players || !book_last || !book_counts) return fail("gmz_engine_play_book: null book array");
+  if (!slot_serial || !slot_draw) return fail("gmz_engine_play_book: null serial or draw array");
+  if (n_openings < 1 || n_openings > (1 << 20)) return fail("gmz_engine_play_book: n_openings must be in [1, 2^20]");
+  if (symmetry != 0 && symmetry != 1) return fail("gmz_engine_play_book: symmetry must be 0 or 1");
+  const size_t n = (size_t)n_openings;
+  if (players_bytes < n)
+    return fail("gmz_engine_play_book: book_players holds " + std::to_string(players_bytes) + " bytes, n_openings = " +
+                std::to_string(n));
+  if (last_bytes < 4 * n || counts_bytes < 4 * n)
+    return fail("gmz_engine_play_book: book_last and book_counts hold " + std::to_string(last_bytes) + " and " +
+                std::to_string(counts_bytes) + " bytes, 4 * n_openings = " + std::to_string(4 * n));
+  if (tally && tally_bytes < 12 * n)
+    return fail("gmz_engine_play_book: tally holds " + std::to_string(tally_bytes) + " bytes, 12 * n_openings = " +
+                std::to_string(12 * n));
+  if (slot_capacity < 1) return fail("gmz_engine_play_book: slot_capacity must be >= the engine's games");
+  if (slot_capacity < e->D.G)
+    return fail("gmz_engine_play_book: slot arrays hold " + std::to_string(slot_capacity) + " slots, the engine has " +
+                std::to_string(e->D.G));
+  if (boards_bytes < n * (size_t)e->D.A)
+    return fail("gmz_engine_play_book: book_boards holds " + std::to_string(boards_bytes) +
+                " bytes, n_openings * board_size^2 = " + std::to_string(n * (size_t)e->D.A));
+  BookArgs B{action, status, book_boards, book_players, book_last, book_counts, n_openings, symmetry, seed,
+             slot_serial, slot_draw, tally};
+  hipLaunchKernelGGL(k_play_book, dim3((e->D.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->D, e->n_in_row, B);
+  GMZ_LAUNCH_CHECK();
   return 0;
 }
 

@@ -23,6 +23,7 @@ from . import _lib
 from .config import from_any
 from ._lib import GmzError, bufs, check, ptr
 from .openings import _has_five, _place_stones, random_openings, seeded_openings  # noqa: F401  (re-exported)
+from .openings import book_draw, check_selfplay_book
 
 
 class HashNetBackend:
@@ -162,6 +163,8 @@ class BatchedSelfPlayEngine:
         self._bud_dev = self._bud_stage = None  # its device copy and the staging pair (made at the first call)
         self._refill = None  # play_refill's slot arrays and pinned read-back buffers (arena)
         self._refill_pending = False
+        self._book = None  # set_book's device book, slot arrays and the host's serial mirror (self-play restarts)
+        self._fill_actions = None  # fill_from_book's actions: -1 everywhere
         self._state_ptrs = None  # device pointers of the engine-owned game state (anchor_move, vcf_move)
         self.vcf_status = self.vcf_moves = None  # the last vcf_move launch's statuses and moves (made at the first)
         self.ab_status = self.ab_moves = None  # the same of ab_move
@@ -382,7 +385,11 @@ class BatchedSelfPlayEngine:
             ended = st != 2
             played = st != 3
             self._n_legal[played & ~ended] -= 1
-            if self._last_reset:
+            if self._last_reset and self._book is not None:  # restarted from the book: the draw is a pure function
+                again = np.nonzero(played & ended)[0]
+                self._book["serial"][again] += 1
+                self._n_legal[again] = self.A - self.book_draws(again)[2]
+            elif self._last_reset:
                 self._n_legal[played & ended] = self.A
             else:
                 self._n_legal[played & ended] = np.maximum(self._n_legal[played & ended] - 1, 0)
@@ -500,10 +507,80 @@ class BatchedSelfPlayEngine:
         (+1/-1 winner, 0 draw, 2 ongoing, 3 untouched)."""
         s = self._stream(stream)
         a = self.action if action is None else torch.as_tensor(action, dtype=torch.int32).to(self.device)
-        check(self.lib.gmz_engine_play(self.handle, ptr(a), ptr(self.status), 1 if reset_finished else 0, s))
+        if self._book is not None and reset_finished:  # ended games restart from the book, not from the empty board
+            if (self._book["serial"] < 0).any():
+                raise ValueError("play: a book is set (set_book); fill_from_book() places the first games")
+            self._play_book(a, s)
+        else:
+            check(self.lib.gmz_engine_play(self.handle, ptr(a), ptr(self.status), 1 if reset_finished else 0, s))
         self._post_status(stream)
         self._last_reset = bool(reset_finished)
         return self.status
+
+    # ------------------------------------------------------------------ self-play's opening book
+    def set_book(self, book, symmetry=True, tally=None):
+        """Ended games restart from a book of openings instead of the empty board (gmz_engine_play_book): ``book`` =
+        (boards, players, last_moves, move_counts) that openings.check_selfplay_book accepts under this engine's
+        configuration, uploaded once, or a BookBuffers that another engine made (the parts of a split engine share
+        one).  Each new game of slot g draws its opening and, with ``symmetry``, one of the square's eight maps from
+        (seed, g + game_offset, the slot's game serial) alone: openings.book_draw gives the host the same draw, so
+        nothing is read back.  ``tally``: an int32 [n, 3] device tensor to count the finished games per opening in
+        (black won, white won, draw; default: a new one, ``book_tally``).  Call fill_from_book() next; from then on
+        play(reset_finished=True) restarts from the book.  Between moves only."""
+        if self._refill is not None:
+            raise ValueError("set_book: not on an engine that play_refill drives (the arena has its own book)")
+        bb = book if isinstance(book, BookBuffers) else BookBuffers(book, self.cfg, self.device)
+        if bb.A != self.A:
+            raise ValueError("set_book: the book's boards are not this engine's size")
+        G, dev = self.G, self.device
+        if tally is None:
+            tally = torch.zeros(bb.n, 3, dtype=torch.int32, device=dev)
+        if not torch.is_tensor(tally) or tally.dtype != torch.int32 or tally.numel() != 3 * bb.n \
+                or tally.device.type != dev.type or not tally.is_contiguous():
+            raise ValueError("set_book: tally must be a contiguous int32 [%d, 3] tensor on %s" % (bb.n, dev))
+        self._book = dict(buf=bb, symmetry=bool(symmetry), tally=tally,
+                          slot_serial=torch.full((G,), -1, dtype=torch.int32, device=dev),
+                          slot_draw=torch.full((G,), -1, dtype=torch.int32, device=dev),
+                          serial=np.full(G, -1, np.int64), keys=np.arange(G, dtype=np.int64) + int(self.ecfg.game_offset))
+        return bb
+
+    @property
+    def book_tally(self):
+        """Finished games per opening of the book, int32 [n, 3] on the device: black won, white won, draw."""
+        return None if self._book is None else self._book["tally"]
+
+    def book_draws(self, slots=None, serials=None):
+        """(opening t, symmetry d, stones) of the games ``serials`` of the slots ``slots`` (default: every slot's
+        current game), computed on the host (openings.book_draw)."""
+        k = self._book
+        slots = np.arange(self.G) if slots is None else np.asarray(slots, dtype=np.int64)
+        serials = k["serial"][slots] if serials is None else np.asarray(serials, dtype=np.int64)
+        t, d = book_draw(self.seed, k["keys"][slots], serials, k["buf"].n, k["symmetry"])
+        return t, d, k["buf"].counts_host[t]
+
+    def _play_book(self, a, s):
+        k = self._book
+        bb = k["buf"]
+        check(self.lib.gmz_engine_play_book(
+            self.handle, ptr(a), ptr(self.status), *bufs(bb.boards, bb.players, bb.last_moves, bb.move_counts), bb.n,
+            self.seed % (1 << 64), 1 if k["symmetry"] else 0, ptr(k["slot_serial"]), ptr(k["slot_draw"]), self.G,
+            *bufs(k["tally"]), s))
+
+    def fill_from_book(self, stream=None):
+        """The first game of every slot from the book (one gmz_engine_play_book launch with every action -1): serial 0
+        everywhere.  The legal counts are known on the host at once; nothing is read back."""
+        k = self._book
+        if k is None:
+            raise ValueError("fill_from_book: no book is set (set_book)")
+        if (k["serial"] >= 0).any():
+            raise ValueError("fill_from_book: the slots hold games from the book already")
+        if self._fill_actions is None:
+            self._fill_actions = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
+        self.sync_status()
+        self._play_book(self._fill_actions, self._stream(stream))
+        k["serial"][:] = 0
+        self._n_legal = (self.A - self.book_draws()[2]).astype(np.int32)
+        self._status_event = None
 
     def _post_status(self, stream):
         """The status and the engine's error word to their pinned buffers behind a play launch, and the event that
@@ -727,6 +804,34 @@ class SplitSelfPlayEngine:
         join_streams(main, self.streams)
         return self.status
 
+    def set_book(self, book, symmetry=True, tally=None):
+        """BatchedSelfPlayEngine.set_book: one book and one tally shared by the parts.  With game_offset the parts
+        draw what one engine with every game draws."""
+        bb = self.engines[0].set_book(book, symmetry, tally)
+        for e in self.engines[1:]:
+            e.set_book(bb, symmetry, self.engines[0].book_tally)
+        return bb
+
+    @property
+    def book_tally(self):
+        return self.engines[0].book_tally
+
+    def book_draws(self, slots=None, serials=None):
+        slots = np.arange(self.G) if slots is None else np.asarray(slots, dtype=np.int64)
+        if serials is None:
+            serials = np.concatenate([e._book["serial"] for e in self.engines])[slots]
+        e = self.engines[0]  # its keys are the slots themselves (game_offset 0), and every part shares seed and book
+        k = e._book
+        t, d = book_draw(e.seed, slots, serials, k["buf"].n, k["symmetry"])
+        return t, d, k["buf"].counts_host[t]
+
+    def fill_from_book(self, stream=None):
+        main = self._fork(stream)
+        for e, st in zip(self.engines, self.streams):
+            with torch.cuda.stream(st):
+                e.fill_from_book()
+        join_streams(main, self.streams)
+
     def set_active(self, mask=None):
         for i, e in enumerate(self.engines):
             e.set_active(None if mask is None else np.asarray(mask).reshape(self.G)[i * self.g:(i + 1) * self.g])
@@ -799,6 +904,19 @@ class MatchBuffers:
         self.winner = torch.full((2 * n,), 2, dtype=torch.int8, device=dev)  # 2 = not finished
         self.length = torch.zeros(2 * n, dtype=torch.int32, device=dev)
         self.moves = torch.full((2 * n, self.A), -1, dtype=torch.int16, device=dev) if record_moves else None
+
+
+class BookBuffers:
+    """Self-play's book of openings on the device (BatchedSelfPlayEngine.set_book), checked by
+    openings.check_selfplay_book under ``cfg``: boards int8 [n, A], players int8 [n] = side to move, last_moves
+    int32 [n], move_counts int32 [n]; ``counts_host`` is the stone count per opening for the host's mirror."""
+
+    def __init__(self, book, cfg, device="cuda"):
+        b, p, lm, mc = check_selfplay_book(book, cfg)
+        self.n, self.A = int(b.shape[0]), int(b.shape[1])
+        dev = torch.device(device)
+        self.boards, self.players, self.last_moves, self.move_counts = (torch.as_tensor(x).to(dev) for x in (b, p, lm, mc))
+        self.counts_host = mc.astype(np.int64)
 
 
 def engine_cfg(c, num_games, flags=0, game_offset=0):

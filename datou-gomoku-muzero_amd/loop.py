@@ -52,14 +52,25 @@ from .weight_sync import broadcast_state_dict
 BUDGET_SEED = 0x5EED0B  # SelfPlay's budget draws: RandomState(seed + BUDGET_SEED), G uniforms per move
 
 
+def start_from_book(eng, hist, book, symmetry=True):
+    """Self-play from a book of openings: the engine restarts ended games from it on the device (set_book,
+    fill_from_book) and the history learns each game's first recorded row from the host's mirror of the draw."""
+    eng.set_book(book, symmetry)
+    eng.fill_from_book()
+    hist.set_book(lambda slots, serials: eng.book_draws(slots, serials)[2])
+
+
 class SelfPlay:
     """G games on this rank's GPU (the self-play half of the worker loop, worker.py)."""
 
     def __init__(self, cfg, num_games, state_dict, seed=0, precision="fp16", streams=None, openings=None,
-                 fast_sims=None, full_prob=1.0):
+                 fast_sims=None, full_prob=1.0, book=None, book_symmetry=True):
         from . import engine as E, network as N
         from .worker import GameHistory
         c = cfg
+        if book is not None and openings is not None:
+            raise ValueError("SelfPlay: give book= (every game starts from the book) or openings= (the first games' "
+                             "positions), not both")
         self.cfg, self.G = c, int(num_games)
         self.net = N.GomokuNetHip(state_dict, c, num_slots=E.hidden_slots(c, self.G), max_rows=self.G,
                                   precision=precision)
@@ -69,6 +80,9 @@ class SelfPlay:
         if openings is not None:  # (boards, players, last_moves, move_counts): e.g. engine.random_openings
             self.eng.set_positions(*openings)
             self.hist.set_start(openings[3])
+        if book is not None:  # (boards, players, last_moves, move_counts): every game of every slot starts from an
+            # opening drawn on the device, with one of the square's eight symmetries (engine.set_book)
+            start_from_book(self.eng, self.hist, book, book_symmetry)
         dev = self.eng.device
         self.missed = (torch.zeros(self.G, dtype=torch.int32, device=dev), torch.zeros(self.G, dtype=torch.int32, device=dev))
         self.pending = None
@@ -122,6 +136,11 @@ class SelfPlay:
         done = self._finished(self.pending)
         self.pending = None
         return done
+
+    def book_tally(self):
+        """Finished games per opening of the book, int32 [n, 3] on the device (black won, white won, draw); None
+        without a book."""
+        return self.eng.book_tally
 
     def load_weights(self, sd):
         self.net.load_state_dict(sd)

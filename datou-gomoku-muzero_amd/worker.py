@@ -12,7 +12,9 @@ workers.py:319-322) when ``initial_model_requests_queue``/``model_update_queue``
 hot-swap between moves (workers.py:332-335); otherwise ``state_dict`` (or seeded synthetic weights).
 ``openings`` (bench only): (boards, players, last_moves, move_counts) the first game of every slot
 starts from, e.g. engine.random_openings — so a short measurement sees games at every stage; their
-records hold the moves searched from there on.  ``worker_mode`` 1 (re-analysis, workers.py:243-305; off by default, config.py:85): the worker locks up to
+records hold the moves searched from there on.  ``book`` (with ``book_symmetry``): a book of openings that
+openings.check_selfplay_book accepts; every game of every slot, not only the first, then starts from an opening drawn
+on the device under one of the square's eight symmetries (engine.set_book).  ``worker_mode`` 1 (re-analysis, workers.py:243-305; off by default, config.py:85): the worker locks up to
 ``reanalysis_games`` stored games of the reference's SQLite database at a time (``db_path``), searches all
 their positions in batches of ``num_games`` on a second engine that shares the network, rewrites their
 slices and posts ``ReAnalysisStatus`` (reanalysis.py).  The current trainer step is the stored
@@ -68,6 +70,8 @@ class GameHistory:
     ``finished`` and the banks, and hands the event of its launch to ``after_ingest``; ``record`` makes its
     stream wait for it, so a bank is never rewritten before an ingest on another stream has read it."""
 
+    _book_counts = None  # set_book: stones of the opening that a slot's game of a given serial starts from
+
     def __init__(self, G, A, device, min_game_len=9):
         assert min_game_len >= 2, "a bank must survive one move after its game ended"
         L = A  # a game has at most A moves
@@ -100,6 +104,17 @@ class GameHistory:
         move; every slot is still on bank 0): their records hold the searched moves from there on."""
         assert self.k == 0, "set_start before the first move"
         self.start[0] = np.asarray(move_counts, dtype=np.int64)
+        self.start[1] = 0
+
+    def set_book(self, counts_of):
+        """Every game of every slot starts from an opening of a book (engine.set_book): ``counts_of(slots, serials)``
+        gives the stones of the openings that the games ``serials`` (0, 1, ... per slot) of ``slots`` start from, e.g.
+        the engine's ``book_draws(...)[2]``.  The current games are the serials 0 (before their first move); when a
+        slot's game is reported finished, the first recorded row of its next game, in the other bank, is set."""
+        assert self.k == 0, "set_book before the first move"
+        self._book_counts = counts_of
+        self.serial = np.zeros(self.G, dtype=np.int64)
+        self.start[0] = np.asarray(counts_of(np.arange(self.G), self.serial), dtype=np.int64)
         self.start[1] = 0
 
     def record(self, boards, players, last_moves, move_counts, policy, value, action):
@@ -170,10 +185,14 @@ class GameHistory:
         if len(fin) == 0:
             return out
         mc, bank, act, mf, mt = (sn[k].numpy() for k in ("mc", "bank", "act", "mf", "mt"))
+        if self._book_counts is not None:  # the slots' next games, in their other banks, start from book openings
+            self.serial[fin] += 1
+            self.start[bank[fin] ^ 1, fin] = np.asarray(self._book_counts(fin, self.serial[fin]), dtype=np.int64)
         for g in fin:
             bk = int(bank[g])
             s0 = int(self.start[bk, g])
-            self.start[bk, g] = 0  # this bank's next game starts from the empty board
+            self.start[bk, g] = 0  # this bank's next game starts from the empty board (set_book: set when the
+            # game between ends)
             if act[g] < 0:
                 continue
             out.append((int(g), bk, s0, int(mc[g]) + 1 - s0, int(st[g]), int(mf[g]), int(mt[g])))
@@ -185,7 +204,8 @@ def gpu_selfplay_worker(worker_id, worker_mode, data_queue, log_status_queue, ui
                         latest_model_step=None, log_queue=None, pause_event=None, *, device=0, num_games=1024,
                         model_update_queue=None, initial_model_requests_queue=None, state_dict=None, cfg=None,
                         seed=0, max_moves=None, emit_move_notices=True, db_path="outputs/training_state.db",
-                        reanalysis_games=64, precision="fp16", move_times=None, streams=None, openings=None):
+                        reanalysis_games=64, precision="fp16", move_times=None, streams=None, openings=None,
+                        book=None, book_symmetry=True):
     logger = logging.getLogger("GpuSelfPlay-%s" % worker_id)
     if log_queue is not None:
         try:
@@ -199,6 +219,8 @@ def gpu_selfplay_worker(worker_id, worker_mode, data_queue, log_status_queue, ui
         except Exception:
             cfg = None
     c = from_any(cfg)
+    if book is not None and openings is not None:
+        raise ValueError("gpu_selfplay_worker: give book= or openings=, not both")
     torch.cuda.set_device(device)
     from . import engine as E, network as N, weights as W
 
@@ -221,7 +243,10 @@ def gpu_selfplay_worker(worker_id, worker_mode, data_queue, log_status_queue, ui
     if openings is not None:  # bench: the first games start from given positions (E.random_openings)
         eng.set_positions(*openings)
         hist.set_start(openings[3])
-    pool = ThreadPoolExecutor(max_workers=4)
+    if book is not None:  # every game of every slot starts from an opening of the book, drawn on the device
+        from .loop import start_from_book
+        start_from_book(eng, hist, book, book_symmetry)
+    pool =ThreadPoolExecutor(max_workers=4)
     moves_done = 0
     # missed-win counters of workers.py:191-203, accumulated on the device move by move by the batched
     # find_winning_moves scan (gmz_game_winning_scan) instead of a Python scan per finished game

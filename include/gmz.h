@@ -248,6 +248,37 @@ int gmz_engine_play_refill(gmz_engine *e, const int32_t *action_dev, int8_t *sta
                            uint32_t *slot_key_dev, uint32_t *slot_ply_dev, int32_t *n_legal_dev, int slot_capacity,
                            int8_t *res_winner_dev, int32_t *res_length_dev, int16_t *res_moves_dev, int moves_stride,
                            int res_capacity, int32_t *finished_dev, void *stream);
+/* gmz_engine_play (no reset) plus self-play's restart from a book of openings, in one launch (additive, ABI stays
+ * 10).  The book: book_boards_dev int8[n][A], book_players_dev int8[n] side to move, book_last_dev int32[n] last
+ * stone or -1, book_counts_dev int32[n] stones, n = n_openings in [1, 2^20].  Per slot g, key = g + game_offset:
+ *   1. do_move(action_dev[g]) + get_game_ended as gmz_engine_play without reset -> status_dev[g] (action < 0, as an
+ *      inactive game's: status 3, the slot is left alone unless item 2 applies);
+ *   2. a slot whose game ended in this call (status +1, -1 or 0) or that never held a game (slot_serial_dev[g] ==
+ *      -1) starts its next game: if a game ended and the slot held a drawn opening (serial >= 0), tally_dev[t'][c]
+ *      += 1 (atomic) for that opening t' = slot_draw_dev[g] >> 3 and c = 0 black won, 1 white won, 2 draw; then
+ *      serial = ++slot_serial_dev[g], the draw (t, d) below, book row t under symmetry d over the slot's board, the
+ *      side to move and the stone count of row t, its last stone under d (-1 stays -1), slot_draw_dev[g] = 8 t + d.
+ * The draw is a pure function of (seed, key, serial), so the host computes it and reads nothing back:
+ *   w(salt) = mix32(mix32((uint32)seed ^ mix32(serial * 0x9E3779B1 + key * 0x85EBCA77)) ^ (uint32)(seed >> 32) ^ salt)
+ *   t = ((uint64)w(GMZ_BOOK_SALT_OPEN) * n) >> 32  (< n),   d = symmetry ? w(GMZ_BOOK_SALT_SYM) & 7 : 0
+ * with mix32 of the device Gumbel noise.  Like a noise row, the draw sees (serial, key) only through the one 32-bit
+ * sum serial * 0x9E3779B1 + key * 0x85EBCA77: two (serial, key) pairs with the same sum draw alike (DESIGN.md §5e,
+ * §8b).  The salts differ from every constant of the noise generator, so no draw word is a noise word.
+ * Symmetry d maps cell (r, c) of the size-S board in this order: bit 0 (r, c) <- (c, r); bit 1 r <- S-1-r; bit 2
+ * c <- S-1-c (the eight maps of the square).
+ * Before the first call slot_serial_dev must hold -1; the first call (every action -1) fills every slot at serial 0.
+ * tally_dev (nullable) int32[n][3] may be shared by engines on different streams.  *_bytes: what each array holds
+ * (>= n * A boards, n players, 4 n last and counts, 12 n tally); slot_capacity: elements of slot_serial_dev /
+ * slot_draw_dev (>= G); symmetry 0 or 1.  Stream-ordered, never synchronises; a bad call is refused before any
+ * launch with nothing written. */
+#define GMZ_BOOK_SALT_OPEN 0xB5297A4Du
+#define GMZ_BOOK_SALT_SYM 0x27D4EB2Fu
+int gmz_engine_play_book(gmz_engine *e, const int32_t *action_dev, int8_t *status_dev, const int8_t *book_boards_dev,
+                         size_t boards_bytes, const int8_t *book_players_dev, size_t players_bytes,
+                         const int32_t *book_last_dev, size_t last_bytes, const int32_t *book_counts_dev,
+                         size_t counts_bytes, int n_openings, uint64_t seed, int symmetry, int32_t *slot_serial_dev,
+                         int32_t *slot_draw_dev, int slot_capacity, int32_t *tally_dev, size_t tally_bytes,
+                         void *stream);
 /* Gumbel(0, 1) noise out_dev f64[G][A] from gmz_engine_begin_move's device generator with keys_dev[g] in place of
  * the game index (g + game_offset) and plies_dev[g] in place of the move counter: row g depends on (seed, key, ply)
  * alone.  Passed to gmz_engine_begin_move as its explicit gumbel_dev.  out_bytes >= G * A * 8. */
